@@ -134,6 +134,57 @@ def _flush_c_stdio():
     sys.stdout.flush()
 
 
+DUMP_BYTES = 60 * 1000 * 1000  # --dump-outputs budget over all fields (under 64 MB)
+DUMP_SEED = 20261015  # fixed: the sampled points are the same in every run with the same arguments
+
+
+def dump_outputs(h, out_dir, world, gather):
+    """Write what a caller of the timed path holds after its last step -- every field of the dycore state (in/out of each
+    acoustic call), the tracers and the surface pressure where the workload has them -- as <out_dir>/<name>.npy in the run's
+    precision.  A field whose compute domain fits its share of DUMP_BYTES is written whole, (sub-domain, i, j[, k]); a larger one as
+    a sample, (sub-domain, point): the same points for every field of one shape, drawn per global sub-domain from DUMP_SEED, so
+    the files of two builds (or of two process counts) compare value for value.  Sub-domains in global rank order."""
+    from pace_amd.dyn_core import STATE_NAMES
+
+    fields = {n: getattr(h.state, n) for n in STATE_NAMES}
+    fields.update(h.tracers)
+    if h.remap is not None:
+        fields["ps"] = h.ps
+    n_glob = h.part.total_ranks
+    mine = {}
+    picks = {}
+    for name, q in fields.items():
+        extent = tuple(q.extent)
+        size = int(np.prod(extent))
+        per_field = DUMP_BYTES // len(fields) // q.storage.element_size()
+        k = per_field // n_glob
+        rows = []
+        for i, r in enumerate(h.layout.local_ranks):
+            v = q.sub(i).view[...]
+            if size * n_glob <= per_field:
+                rows.append(v.detach().cpu().numpy())
+                continue
+            key = (extent, r)
+            if key not in picks:
+                flat = np.sort(np.random.default_rng([DUMP_SEED, r]).choice(size, k, replace=False))
+                picks[key] = [torch.as_tensor(ix, device=v.device) for ix in np.unravel_index(flat, extent)]
+            rows.append(v[tuple(picks[key])].detach().cpu().numpy())
+        mine[name] = dict(zip(h.layout.local_ranks, rows))
+    parts = [mine] if world == 1 else gather(mine)
+    if parts is None:
+        return None
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name in fields:
+        by_rank = {}
+        for p in parts:
+            by_rank.update(p[name])
+        a = np.stack([by_rank[r] for r in sorted(by_rank)])  # (--emulate-share: the sub-domains of the one process played)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        total += a.nbytes
+    return len(fields), total
+
+
 def _hbm_used_gb():
     try:
         free, total = torch.cuda.mem_get_info()
@@ -165,7 +216,11 @@ def main():
                     "device-local or looped-back halo transport -- nothing in a step touches the host there; the RCCL launch path of an N-GPU run stays exactly as "
                     "tested).  Same kernels, same values; what it removes is the launch path (~110 launches per sub-step), which matters for the small per-GPU shares. "
                     "Implies --no-op-timing (event pairs are not part of a replay); the line says graph_replay: true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the state the last step left (every dycore-state field, "
+                    "tracers, ps) as DIR/<name>.npy in the run's precision: whole compute domains, or a fixed seeded sample of each when that would exceed 60 MB")
     a = ap.parse_args()
+    if a.steps < 1:
+        sys.exit("--steps must be at least 1")
 
     from pace_amd.harness import CONFIGS, DycoreHarness
 
@@ -282,6 +337,18 @@ def main():
         tt = torch.tensor([elapsed], device=f"cuda:{local_rank}", dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if a.dump_outputs:
+
+        def gather_to_root(mine):
+            import torch.distributed as dist
+
+            every = [None] * world if rank == 0 else None
+            dist.gather_object(mine, every, dst=0)
+            return every
+
+        dumped = dump_outputs(h, a.dump_outputs, world, gather_to_root)
+        if dumped:
+            print(f"[bench] wrote {dumped[0]} arrays ({dumped[1] / 1e6:.1f} MB) to {a.dump_outputs}", file=sys.stderr, flush=True)
     sanity = h.sanity()
     ok = all(v[2] for v in sanity.values())
 
