@@ -357,6 +357,14 @@ int fv3_remap(fv3_ctx *, int n_tracers, const fv3_field *const *tracers, const f
               const fv3_field *u, const fv3_field *v, const fv3_field *w, const fv3_field *cappa, const fv3_field *ps,
               const fv3_field *wsd, void *stream);
 
+/* CubedToLatLon (the last operator of fv_dynamics: FV3 fv_grid_utils.F90 c2l_ord4 / c2l_ord2; pyFV3 CubedToLatLon, savepoint
+ * FVDynamics-Out ua / va [REF tests/savepoint/thresholds/fv_dynamics.yaml]).  D-grid u, v -> ua, va on the compute cells in earth
+ * coordinates (eastward, northward).  order: c2l_ord, 4 (the reference's default) or 2.  a11 .. a22: the cell-centre rotation
+ * terms (2-D fields, shape[2] == 1; GridData a11 .. a22).  Order 4 reads u at j-1 .. j+2 and v at i-1 .. i+2: the caller updates
+ * the D-grid halo of u, v before the call.  Levels 0 .. nz-1; nothing outside the compute cells of ua / va is written. */
+int fv3_cubed_to_latlon(fv3_ctx *, int order, const fv3_field *u, const fv3_field *v, const fv3_field *ua, const fv3_field *va,
+                        const fv3_field *a11, const fv3_field *a12, const fv3_field *a21, const fv3_field *a22, void *stream);
+
 /* ---- per-operator timing (HIP events on the operators' stream) --------------------------------- */
 enum fv3_op {
   FV3_OP_C_SW = 0,

@@ -99,6 +99,8 @@ class AcousticDynamicsConfig:
     tau: float = 10.0
     use_old_omega: bool = True
     breed_vortex_inline: bool = False
+    # CubedToLatLon at the end of fv_dynamics: 4 (c2l_ord4) unless the yaml says otherwise, or 2 (c2l_ord2)
+    c2l_ord: int = 4
 
     def validate(self):
         """The kernels are specialised like the reference configs; anything else fails loudly."""
@@ -122,6 +124,8 @@ class AcousticDynamicsConfig:
                 bad.append(f"{h}={getattr(self, h)} (5 or 6)")
         if not (0 <= self.nord <= 3):
             bad.append("nord outside 0..3")
+        if self.c2l_ord not in (2, 4):
+            bad.append(f"c2l_ord={self.c2l_ord} (2 or 4)")
         if self.do_skeb or self.do_f3d or self.inline_q:
             bad.append("do_skeb/do_f3d/inline_q")
         if bad:

@@ -71,6 +71,8 @@ def main(argv=None):
     ap.add_argument("--save-restart", default=None, help="write restart_dycore_state_<rank>.nc files there after the last step [REF state.py:114-123]")
     ap.add_argument("--tracers", type=int, default=0, help="advect N synthetic tracers after every acoustic call (TracerAdvection, hord_tr from the yaml)")
     ap.add_argument("--remap", action="store_true", help="Lagrangian-to-Eulerian remap after every acoustic call (with --tracers: the body of DynamicalCore.step_dynamics)")
+    ap.add_argument("--latlon-winds", action="store_true",
+                    help="CubedToLatLon at the end of every step (c2l_ord from the yaml, default 4): state ua / va become the eastward / northward cell-centre winds")
     a = ap.parse_args(argv)
     run, dy, ignored = load_config(a.config)
 
@@ -86,7 +88,7 @@ def main(argv=None):
         say(f"backend {run['backend']!r} requested by the yaml -> running 'hip:gfx950' (the only backend of this build)")
     if not (run["dycore_only"] and run["disable_step_physics"]):
         say("physics is outside this build: running the dycore-only loop")
-    say("step = k_split x [acoustic dynamics" + (f", advection of {a.tracers} tracers" if a.tracers else "") + (", vertical remap" if a.remap else "") + "]"
+    say("step = k_split x [acoustic dynamics" + (f", advection of {a.tracers} tracers" if a.tracers else "") + (", vertical remap" if a.remap else "") + "]" + (", then CubedToLatLon" if a.latlon_winds else "")
         + ("" if (a.tracers and a.remap) else "  (--tracers N --remap add the rest of step_dynamics)"))
     if run["init"] == "analytic" and str(run["case"]).startswith("baroclinic"):
         init = "baroclinic"
@@ -109,7 +111,7 @@ def main(argv=None):
     kw = {k: dy[k] for k in ("k_split", "n_split") if k in dy}
     h = DycoreHarness(nx_tile=run["nx_tile"], nz=run["nz"], layout=run["layout"], dt_atmos=run["dt_atmos"], world_size=world, proc=rank,
                       device=f"cuda:{local_rank}", dtype=dtype, verbose=(rank == 0), init=init, config_overrides={k: v for k, v in dy.items() if k not in ("k_split", "n_split")},
-                      n_tracers=a.tracers, hord_tr=int(dy.get("hord_tr", 8)), remap=a.remap, **kw)
+                      n_tracers=a.tracers, hord_tr=int(dy.get("hord_tr", 8)), remap=a.remap, latlon_winds=a.latlon_winds, **kw)
     if run["device_sync"]:
         h.sf.set_device_sync(True)
     if a.restart:

@@ -144,7 +144,7 @@ _GRID_2D = (
     "dx dy dxa dya dxc dyc rdx rdy rdxa rdya rdxc rdyc area rarea area_c rarea_c "
     "cosa sina rsina cosa_u cosa_v cosa_s sina_u sina_v rsin_u rsin_v rsin2 "
     "sin_sg1 sin_sg2 sin_sg3 sin_sg4 sin_sg5 cos_sg1 cos_sg2 cos_sg3 cos_sg4 "
-    "fC f0 del6_u del6_v divg_u divg_v lon lat lon_agrid lat_agrid"
+    "fC f0 del6_u del6_v divg_u divg_v lon lat lon_agrid lat_agrid a11 a12 a21 a22"
 ).split()
 
 
@@ -309,6 +309,19 @@ def make_grid(
         return np.minimum(1.0, np.sqrt(np.maximum(0.0, 1.0 - cv * cv)))
 
     sin = {1: _sin(cos1), 2: _sin(cos2), 3: _sin(cos3), 4: _sin(cos4), 5: _sin(cos5)}
+
+    # Cubed-sphere -> lat-lon rotation at the cell centre (FV3 fv_grid_utils.F90, init_cubed_to_latlon): the local unit
+    # vectors ec1 / ec2 projected on the local east (vlon) and north (vlat = A x vlon) give z11 .. z22; inverting the
+    # covariant components u = V.ec1, v = V.ec2 of a wind V = ue vlon + vn vlat divides by sin_sg5.  The 0.5 takes the
+    # "2 x" of c2l_ord2 / c2l_ord4's cell-centre interpolants.  Needed on compute cells only (the cube-corner halo blocks
+    # keep whatever the x-direction corner fill of the grid points gives).
+    lon_A, _lat_A = lonlat(A)
+    vlon = np.stack([-np.sin(lon_A), np.cos(lon_A), np.zeros_like(lon_A)], axis=-1)
+    vlat = _normalize(np.cross(A, vlon))
+    z11, z12 = np.sum(ec1 * vlon, -1), np.sum(ec1 * vlat, -1)
+    z21, z22 = np.sum(ec2 * vlon, -1), np.sum(ec2 * vlat, -1)
+    rs5 = 1.0 / np.maximum(TINY, sin[5])  # (degenerate only in cube-corner halo cells)
+    c2l = {"a11": 0.5 * z22 * rs5, "a12": -0.5 * z12 * rs5, "a21": -0.5 * z21 * rs5, "a22": 0.5 * z11 * rs5}
     cos = {1: cos1, 2: cos2, 3: cos3, 4: cos4, 5: cos5}
 
     # Cube-corner halo blocks have no owner: fill the cell-centred terms from the
@@ -460,6 +473,8 @@ def make_grid(
         put(f"sin_sg{k}", sin[k])
         put(f"cos_sg{k}", cos[k])
     put("sin_sg5", sin[5])  # cell centre (tracer_2d_1l's Courant-number bound)
+    for k, a in c2l.items():
+        put(k, a)  # CubedToLatLon
     put("fC", fC), put("f0", f0)
     put("del6_u", del6_u), put("del6_v", del6_v), put("divg_u", divg_u), put("divg_v", divg_v)
     put("lon", lon_c), put("lat", lat_c), put("lon_agrid", lon_a), put("lat_agrid", lat_a)

@@ -5,7 +5,8 @@ the hot path with ``dycore_only: true, disable_step_physics: true``
 One "step" = ``k_split`` calls of AcousticDynamics, timed like the reference ("mainloop" timer, first step dropped
 [REF .jenkins/print_performance_number.py:13-14]).  The headline workload is the acoustic loop alone; ``n_tracers`` adds the
 sub-cycled tracer advection after every acoustic call and ``remap`` the Lagrangian-to-Eulerian remap after that (SURVEY §8f-3:
-together the body of ``DynamicalCore.step_dynamics``; no physics, no moist thermodynamics).
+together the body of ``DynamicalCore.step_dynamics``; no physics, no moist thermodynamics); ``latlon_winds`` the CubedToLatLon that
+ends ``fv_dynamics`` (eastward / northward ``ua``, ``va``).
 """
 from __future__ import annotations
 
@@ -64,6 +65,7 @@ class DycoreHarness:
         ak=None,
         bk=None,
         loopback: bool = False,
+        latlon_winds: bool = False,
         _testing_token=None,
     ):
         self.c = get_constants()
@@ -134,12 +136,19 @@ class DycoreHarness:
 
             self.remap = LagrangianToEulerian(self.sf, self.sf.quantity_factory, self.grids)
             self.ps = self.sf.quantity_factory.zeros(("x", "y"), "Pa")
+        # CubedToLatLon once per step, after the k_split loop (where fv_dynamics runs it): state.ua / state.va become the eastward /
+        # northward cell-centre winds.  Off by default: without it ua / va keep what the last c_sw left (local A-grid components).
+        self.cubed_to_latlon = None
+        if latlon_winds:
+            from .stencils import CubedToLatLon
+
+            self.cubed_to_latlon = CubedToLatLon(self.sf, self.sf.quantity_factory, self.grids, order=self.cfg.c2l_ord, comm=self.layout)
         self.cells_local = self.part.nx * self.part.ny * nz * len(self.grids)
         self.cells_global = nx_tile * nx_tile * 6 * nz
 
     def step(self, timer=None):
         """One model step of the dycore-only driver: k_split acoustic-dynamics calls (each followed by tracer advection and the
-        vertical remap where the harness was built with them).  ``timer`` (pace_amd.timer.Timer): the reference's timer names inside
+        vertical remap where the harness was built with them), then -- with ``latlon_winds`` -- CubedToLatLon once.  ``timer`` (pace_amd.timer.Timer): the reference's timer names inside
         ``DynamicalCore.step_dynamics`` -- "DynCore" around the acoustic dynamics, "TracerAdvection", "Remapping"
         [REF tests/main/driver/test_driver.py:77-121]."""
         from .timer import NullTimer
@@ -159,6 +168,9 @@ class DycoreHarness:
                 s = self.state
                 with timer.clock("Remapping"):
                     self.remap(self.tracers, s.pt, s.delp, s.delz, s.peln, s.pe, s.pk, s.pkz, s.u, s.v, s.w, s.cappa, self.ps, self.dyn._wsd)
+        if self.cubed_to_latlon is not None:
+            with timer.clock("CubedToLatLon"):
+                self.cubed_to_latlon(self.state.u, self.state.v, self.state.ua, self.state.va)
 
     def close(self):
         """Destroy the library context now (scratch, streams, the RCCL communicator) instead of at garbage collection -- the end of a

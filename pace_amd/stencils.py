@@ -275,3 +275,43 @@ class LagrangianToEulerian(_Op):
                                    ps.fref, wsd.fref, self.sf.stream_handle)
         if st != 0:
             raise _lib.Fv3Error(f"fv3_remap failed ({st}): " + self.sf.lib.fv3_last_error(self.sf.ctx).decode())
+
+
+class CubedToLatLon(_Op):
+    """``CubedToLatLon`` (FV3 ``fv_grid_utils.F90``: ``c2l_ord4`` / ``c2l_ord2``), the last operator of ``fv_dynamics``: the D-grid
+    winds ``u``, ``v`` become the cell-centre winds ``ua`` (eastward) and ``va`` (northward) on the compute cells.  ``order``
+    is ``c2l_ord`` (4, the reference's default, or 2).  Order 4 reads one row / column of halo: like the reference, the call
+    starts with a D-grid vector halo update of ``u``, ``v`` (``comm``: a :class:`pace_amd.halo.Layout`, None = every rank in this
+    process).  Call as the reference's ``cubed_to_latlon(u, v, ua, va)``."""
+
+    def __init__(self, stencil_factory, quantity_factory=None, grid_data=None, order=4, comm=None):
+        super().__init__(stencil_factory, quantity_factory, grid_data)
+        self.order = int(order)
+        if self.order not in (2, 4):
+            raise ValueError(f"CubedToLatLon: order {order} (c2l_ord is 2 or 4)")
+        self.comm = comm
+        # the rotation terms of the context's sub-domains, uploaded once (2-D fields like phis)
+        qf = self.qf
+        self.a11, self.a12, self.a21, self.a22 = (qf.from_array([g.fields[n] for g in self.sf.grids], ("x", "y")) for n in ("a11", "a12", "a21", "a22"))
+        self._updater = None
+        self._bound = None
+
+    def _uv_updater(self, u, v):
+        from .halo import HaloExchanger, Layout
+        from .topology import CubedSpherePartitioner
+
+        key = (id(u), id(v))
+        if self._bound != key:
+            lay = self.comm
+            if lay is None:
+                cfg = self.sf.config
+                lay = Layout(CubedSpherePartitioner(cfg.npx - 1, tuple(cfg.layout)), 1, 0)
+            ex = HaloExchanger.shared(self.sf, lay, group=getattr(lay, "group", None))
+            self._updater = ex.updater("dgrid", [(u, v)])
+            self._bound = key
+        return self._updater
+
+    def __call__(self, u, v, ua, va):
+        if self.order == 4:
+            self._uv_updater(u, v).update()  # mpp_update_domains(u, v, DGRID_NE) inside c2l_ord4
+        self.sf.call("cubed_to_latlon", self.order, u.fref, v.fref, ua.fref, va.fref, self.a11.fref, self.a12.fref, self.a21.fref, self.a22.fref)
