@@ -16,6 +16,34 @@ C1 = -2.0 / 14.0
 C2 = 11.0 / 14.0
 C3 = 5.0 / 14.0
 
+# Opt-in branch counters for the tests: number of evaluated points that took each limiter branch.  None = off (the default);
+# counting never changes a value.
+_COUNTS = None
+COUNTERS = ("ppm8_dm_clamped", "ppm8_edge_clamped", "ppm8_bl_clamped", "ppm8_br_clamped", "pert_ppm_lo", "pert_ppm_hi", "pert_ppm_flat",
+            "smt5_true_hord5", "smt5_false_hord5", "smt5_true_hord6", "smt5_false_hord6")
+
+
+def enable_counters(on: bool = True) -> None:
+    global _COUNTS
+    _COUNTS = dict.fromkeys(COUNTERS, 0) if on else None
+
+
+def reset_counters() -> None:
+    if _COUNTS is not None:
+        enable_counters(True)
+
+
+def counters():
+    """Counts since the last reset: hord 8 -- the monotonized slope dm limited by the local range, the tile-edge value clamped
+    to the range of its four cells, bl / br limited to 2 |dm|, pert_ppm's a6da < -da2 / a6da > da2 / flattening (bl br >= 0);
+    hord 5 / 6 -- the smt5 switch true / false."""
+    return dict(_COUNTS or dict.fromkeys(COUNTERS, 0))
+
+
+def _count(name, mask):
+    if _COUNTS is not None:
+        _COUNTS[name] += int(np.count_nonzero(mask))
+
 
 def _col(D, a, i, j0, j1):
     o = D.o
@@ -71,6 +99,10 @@ def _flux_from_blbr(D, q, c, bl, br, j0, j1, mord, cfl_scale=None):
     else:
         # (FV3_ALT=smt5_lim_fac: tp_core.F90 writes abs(lim_fac * b0) with the namelist default lim_fac = 1 -- DESIGN §2, uncertain restatement 3)
         smt5 = ((1.0 if alt("smt5_lim_fac") else 3.0) * np.abs(b0)) < np.abs(bl - br)
+    if _COUNTS is not None:
+        R = S(D.is_ - 1, D.ie + 1, j0, j1)  # (the cells whose smt5 the fluxes read)
+        _count(f"smt5_true_hord{mord}", smt5[R])
+        _count(f"smt5_false_hord{mord}", ~smt5[R])
     R0 = S(D.is_, D.ie + 1, j0, j1)
     Rm = S(D.is_ - 1, D.ie, j0, j1)
     cc = c[R0]
@@ -95,6 +127,9 @@ def _pert_ppm_full(bl, br):
     da2 = da1 * da1
     a6da = 3.0 * (bl + br) * da1
     opposite = bl * br < 0.0
+    _count("pert_ppm_lo", opposite & (a6da < -da2))
+    _count("pert_ppm_hi", opposite & ~(a6da < -da2) & (a6da > da2))
+    _count("pert_ppm_flat", ~opposite)
     nbr = np.where(opposite & (a6da < -da2), -2.0 * bl, br)
     nbl = np.where(opposite & ~(a6da < -da2) & (a6da > da2), -2.0 * br, bl)
     return np.where(opposite, nbl, 0.0), np.where(opposite, nbr, 0.0)
@@ -115,6 +150,7 @@ def xppm8(D: Dom, q, c, j0, j1):
     hi = np.maximum(np.maximum(q[Rm], q[R]), q[Rp]) - q[R]
     lo = q[R] - np.minimum(np.minimum(q[Rm], q[R]), q[Rp])
     dm[R] = np.copysign(np.minimum(np.minimum(np.abs(xt), hi), lo), xt)
+    _count("ppm8_dm_clamped", np.minimum(hi, lo) < np.abs(xt))
     is1 = max(3, is_ - 1) if D.west else is_ - 1
     ie1 = min(npx - 3, ie + 1) if D.east else ie + 1
     al = np.zeros_like(q)
@@ -123,6 +159,8 @@ def xppm8(D: Dom, q, c, j0, j1):
     bl, br = np.zeros_like(q), np.zeros_like(q)
     R, Rp = S(is1, ie1, j0, j1), S(is1 + 1, ie1 + 1, j0, j1)
     x2 = 2.0 * dm[R]
+    _count("ppm8_bl_clamped", np.abs(x2) < np.abs(al[R] - q[R]))
+    _count("ppm8_br_clamped", np.abs(x2) < np.abs(al[Rp] - q[R]))
     bl[R] = -np.copysign(np.minimum(np.abs(x2), np.abs(al[R] - q[R])), x2)
     br[R] = np.copysign(np.minimum(np.abs(x2), np.abs(al[Rp] - q[R])), x2)
 
@@ -149,7 +187,9 @@ def xppm8(D: Dom, q, c, j0, j1):
         xt = _edge_mean(Q(-1), Q(0), Q(1), Q(2), M(-1), M(0), M(1), M(2))
         # iord >= 8: the two-sided tile-edge value stays inside the range of the four cells around the edge
         # (tp_core.F90 xppm, "xt = max(xt, min(q1(-1), q1(0), q1(1), q1(2))); xt = min(xt, max(...))"; pyFV3 xppm.xt_dxa_edge_0 with xt_minmax)
+        xt0 = xt
         xt = np.minimum(np.maximum(xt, np.minimum(np.minimum(Q(-1), Q(0)), np.minimum(Q(1), Q(2)))), np.maximum(np.maximum(Q(-1), Q(0)), np.maximum(Q(1), Q(2))))
+        _count("ppm8_edge_clamped", xt != xt0)
         put(bl, 1, xt - Q(1))
         put(br, 0, xt - Q(0))
         put(bl, 0, S14 * DM(-1) + S11 * (Q(-1) - Q(0)))
@@ -161,8 +201,10 @@ def xppm8(D: Dom, q, c, j0, j1):
     if D.east:
         put(bl, npx - 2, AL(npx - 2) - Q(npx - 2))
         xt = _edge_mean(Q(npx - 2), Q(npx - 1), Q(npx), Q(npx + 1), M(npx - 2), M(npx - 1), M(npx), M(npx + 1))
+        xt0 = xt
         xt = np.minimum(np.maximum(xt, np.minimum(np.minimum(Q(npx - 2), Q(npx - 1)), np.minimum(Q(npx), Q(npx + 1)))),
                         np.maximum(np.maximum(Q(npx - 2), Q(npx - 1)), np.maximum(Q(npx), Q(npx + 1))))
+        _count("ppm8_edge_clamped", xt != xt0)
         put(br, npx - 1, xt - Q(npx - 1))
         put(bl, npx, xt - Q(npx))
         put(br, npx, S11 * (Q(npx + 1) - Q(npx)) - S14 * DM(npx + 1))

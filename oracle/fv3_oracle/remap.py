@@ -34,7 +34,35 @@ def _load():
         _lib = C.CDLL(build_lib())
         _lib.remap_one.argtypes = [C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_double, C.c_int, C.c_double]
         _lib.remap_rank.argtypes = [C.POINTER(_Geom)] + [C.c_void_p] * 15 + [C.c_int, C.c_void_p]
+        _lib.remap_counters_enable.argtypes = [C.c_int]
+        _lib.remap_counters.argtypes = [C.c_void_p]
+        _lib.remap_counters.restype = C.c_int
     return _lib
+
+
+# names of the oracle's branch counters, in the order of the C enum (remap_oracle.c, RC_*)
+COUNTERS = ("iv0_nonpos", "iv0_negmin_flat", "iv0_negmin_top", "iv0_negmin_bot", "iv12_flat", "iv12_a6da_lo", "iv12_a6da_hi", "constrain_iv0",
+            "top_iv0", "top_ivm1", "bot_iv0", "bot_ivm1", "flat_2dz", "flat_qmin", "span3")
+
+
+def enable_counters(on: bool = True) -> None:
+    """Count the limiter branches the oracle takes (tests only; off by default, never changes a result)."""
+    _load().remap_counters_enable(int(bool(on)))
+
+
+def reset_counters() -> None:
+    _load().remap_counters_reset()
+
+
+def counters() -> Dict[str, int]:
+    """Branch counts since the last reset: cs_limiters iv = 0 (mean <= 0; negative local minimum: flat / refit from the top / from
+    the bottom edge) and iv = 1 / 2 (flat; a6da < -da2; a6da > da2), the iv = 0 large-scale constraint clamping an edge to 0, the
+    top / bottom edge clamps for iv = 0 and iv = -1, interior flattening as a 2-delta-z wave and by the qmin clause alone, and
+    target layers that cover 3 or more source layers."""
+    lib = _load()
+    out = (C.c_long * lib.remap_counters(None))()
+    lib.remap_counters(C.cast(out, C.c_void_p))
+    return dict(zip(COUNTERS, (int(x) for x in out)))
 
 
 def _p(a):

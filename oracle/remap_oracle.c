@@ -29,19 +29,50 @@ static double dmax(double a, double b) { return a > b ? a : b; }
 static double dmin3(double a, double b, double c) { return dmin(a, dmin(b, c)); }
 static double dmax3(double a, double b, double c) { return dmax(a, dmax(b, c)); }
 
+/* Opt-in branch counters for the tests (remap_counters_enable): how often each limiter branch of the profile and each kind of
+ * target layer was taken.  Off by default; counting never changes a value. */
+enum {
+  RC_IV0_NONPOS,       /* cs_limiters iv = 0: mean <= 0, flat */
+  RC_IV0_NEGMIN_FLAT,  /* iv = 0, negative local minimum, the mean below both edges: flat */
+  RC_IV0_NEGMIN_TOP,   /* iv = 0, negative local minimum, a3 > a2: refit from the top edge */
+  RC_IV0_NEGMIN_BOT,   /* iv = 0, negative local minimum, otherwise: refit from the bottom edge */
+  RC_IV12_FLAT,        /* cs_limiters iv = 1 / 2: flat (mean outside the edges / an extremum) */
+  RC_IV12_A6DA_LO,     /* iv = 1 / 2: a6da < -da2 */
+  RC_IV12_A6DA_HI,     /* iv = 1 / 2: a6da > da2 */
+  RC_CONSTRAIN_IV0,    /* large-scale constraint at a local minimum, iv = 0: the edge value clamped to 0 */
+  RC_TOP_IV0,          /* top edge clamped to 0, iv = 0 */
+  RC_TOP_IVM1,         /* top edge set to 0, iv = -1 (sign change against the mean) */
+  RC_BOT_IV0,          /* bottom edge clamped to 0, iv = 0 */
+  RC_BOT_IVM1,         /* bottom edge set to 0, iv = -1 */
+  RC_FLAT_2DZ,         /* interior layer flattened as a 2-delta-z wave */
+  RC_FLAT_QMIN,        /* interior layer flattened by the qmin clause alone (an extremum below the floor) */
+  RC_SPAN3,            /* a target layer that covers 3 or more source layers */
+  RC_N
+};
+static long rc_counts[RC_N];
+static int rc_on = 0;
+#define RC(i) \
+  do {        \
+    if (rc_on) ++rc_counts[i]; \
+  } while (0)
+
 /* cs_limiters on one cell: a[0] = mean, a[1] = top edge, a[2] = bottom edge, a[3] = curvature */
 static void cs_limiters(int extm, double *a, int iv) {
   if (iv == 0) { /* positive definite */
     if (a[0] <= 0.0) {
+      RC(RC_IV0_NONPOS);
       a[1] = a[0], a[2] = a[0], a[3] = 0.0;
     } else if (fabs(a[2] - a[1]) < -a[3]) {
       if (a[0] + 0.25 * (a[2] - a[1]) * (a[2] - a[1]) / a[3] + a[3] * R12 < 0.0) { /* the local minimum is negative */
         if (a[0] < a[2] && a[0] < a[1]) {
+          RC(RC_IV0_NEGMIN_FLAT);
           a[2] = a[0], a[1] = a[0], a[3] = 0.0;
         } else if (a[2] > a[1]) {
+          RC(RC_IV0_NEGMIN_TOP);
           a[3] = 3.0 * (a[1] - a[0]);
           a[2] = a[1] - a[3];
         } else {
+          RC(RC_IV0_NEGMIN_BOT);
           a[3] = 3.0 * (a[2] - a[0]);
           a[1] = a[2] - a[3];
         }
@@ -50,13 +81,16 @@ static void cs_limiters(int extm, double *a, int iv) {
   } else {
     int flat = iv == 1 ? ((a[0] - a[1]) * (a[0] - a[2]) >= 0.0) : extm;
     if (flat) {
+      RC(RC_IV12_FLAT);
       a[1] = a[0], a[2] = a[0], a[3] = 0.0;
     } else {
       double da1 = a[2] - a[1], da2 = da1 * da1, a6da = a[3] * da1;
       if (a6da < -da2) {
+        RC(RC_IV12_A6DA_LO);
         a[3] = 3.0 * (a[1] - a[0]);
         a[2] = a[1] - a[3];
       } else if (a6da > da2) {
+        RC(RC_IV12_A6DA_HI);
         a[3] = 3.0 * (a[2] - a[0]);
         a[1] = a[2] - a[3];
       }
@@ -111,7 +145,10 @@ static void cs_profile9(double qs, double a4[][4], const double *delp, int km, i
       q[k] = dmax(q[k], dmin(a4[k - 1][0], a4[k][0]));
     } else { /* a local minimum */
       q[k] = dmin(q[k], dmax(a4[k - 1][0], a4[k][0]));
-      if (iv == 0) q[k] = dmax(0.0, q[k]);
+      if (iv == 0) {
+        if (q[k] < 0.0) RC(RC_CONSTRAIN_IV0);
+        q[k] = dmax(0.0, q[k]);
+      }
     }
   }
   q[km - 1] = dmin(q[km - 1], dmax(a4[km - 2][0], a4[km - 1][0]));
@@ -128,9 +165,13 @@ static void cs_profile9(double qs, double a4[][4], const double *delp, int km, i
   }
   /* sub-grid constraints: the two top and two bottom layers always monotone */
   if (iv == 0) {
+    if (a4[0][1] < 0.0) RC(RC_TOP_IV0);
     a4[0][1] = dmax(0.0, a4[0][1]);
   } else if (iv == -1) {
-    if (a4[0][1] * a4[0][0] <= 0.0) a4[0][1] = 0.0;
+    if (a4[0][1] * a4[0][0] <= 0.0) {
+      RC(RC_TOP_IVM1);
+      a4[0][1] = 0.0;
+    }
   }
   a4[0][3] = 3.0 * (2.0 * a4[0][0] - (a4[0][1] + a4[0][2]));
   cs_limiters(extm[0], a4[0], 1);
@@ -139,6 +180,10 @@ static void cs_profile9(double qs, double a4[][4], const double *delp, int km, i
   /* interior, kord = 9 */
   for (k = 2; k < km - 2; ++k) {
     if ((extm[k] && extm[k - 1]) || (extm[k] && extm[k + 1]) || (use_qmin && extm[k] && a4[k][0] < qmin)) {
+      if ((extm[k] && extm[k - 1]) || (extm[k] && extm[k + 1]))
+        RC(RC_FLAT_2DZ);
+      else
+        RC(RC_FLAT_QMIN);
       a4[k][1] = a4[k][0], a4[k][2] = a4[k][0], a4[k][3] = 0.0; /* grid-scale 2-delta-z wave (or below the floor): flat */
     } else {
       a4[k][3] = 6.0 * a4[k][0] - 3.0 * (a4[k][1] + a4[k][2]);
@@ -155,9 +200,13 @@ static void cs_profile9(double qs, double a4[][4], const double *delp, int km, i
     if (iv == 0) cs_limiters(extm[k], a4[k], 0);
   }
   if (iv == 0) {
+    if (a4[km - 1][2] < 0.0) RC(RC_BOT_IV0);
     a4[km - 1][2] = dmax(0.0, a4[km - 1][2]);
   } else if (iv == -1) {
-    if (a4[km - 1][2] * a4[km - 1][0] <= 0.0) a4[km - 1][2] = 0.0;
+    if (a4[km - 1][2] * a4[km - 1][0] <= 0.0) {
+      RC(RC_BOT_IVM1);
+      a4[km - 1][2] = 0.0;
+    }
   }
   a4[km - 2][3] = 3.0 * (2.0 * a4[km - 2][0] - (a4[km - 2][1] + a4[km - 2][2]));
   cs_limiters(extm[km - 2], a4[km - 2], 2);
@@ -187,6 +236,7 @@ static void remap_column(int km, const double *pe1, const double *q1, const doub
         } else { /* fractional first layer, whole layers, fractional last layer */
           double qsum = (pe1[l + 1] - pe2[k]) * (a4[l][1] + 0.5 * (a4[l][3] + a4[l][2] - a4[l][1]) * (1.0 + pl) - a4[l][3] * (R3 * (1.0 + pl * (1.0 + pl))));
           for (m = l + 1; m < km; ++m) {
+            if (m == l + 2) RC(RC_SPAN3); /* a third source layer contributes */
             if (pe2[k + 1] > pe1[m + 1]) {
               qsum = qsum + dp1[m] * a4[m][0];
             } else {
@@ -311,6 +361,14 @@ void remap_rank(const remap_geom *g, const double *ak, const double *bk, double 
   for (i = nh; i < nh + g->nx; ++i)
     for (j = nh; j < nh + g->ny; ++j)
       for (k = 0; k < nz; ++k) AT(delp, i, j, k) = AT(pe, i, j, k + 1) - AT(pe, i, j, k);
+}
+
+/* the branch counters: on / off, reset, read (RC_N values into out; returns RC_N) */
+void remap_counters_enable(int on) { rc_on = on; }
+void remap_counters_reset(void) { memset(rc_counts, 0, sizeof(rc_counts)); }
+int remap_counters(long *out) {
+  if (out) memcpy(out, rc_counts, sizeof(rc_counts));
+  return RC_N;
 }
 
 /* single-column entry for the property tests */
