@@ -15,6 +15,42 @@ from .a2b_ord4 import a2b_ord4
 from .fvtp2d import del6_vt_flux, fv_tp_2d
 from .util import Dom, alt, copy_corners, fill_4corners
 
+# Opt-in branch counters for the tests (as fv3_oracle.ppm): number of evaluated points that took each branch.  None = off (the
+# default); counting never changes a value.
+_COUNTS = None
+COUNTERS = ("sim1_floor", "sim1_free", "dzc_limited", "dzc_free", "dzd_limited", "dzd_free", "dzc_upwind_pos_x", "dzc_upwind_neg_x", "dzc_upwind_pos_y",
+            "dzc_upwind_neg_y", "heat_limited", "heat_free", "ray_damped", "ray_nudged_only", "ray_none")
+
+
+def enable_counters(on: bool = True) -> None:
+    global _COUNTS
+    _COUNTS = dict.fromkeys(COUNTERS, 0) if on else None
+
+
+def reset_counters() -> None:
+    if _COUNTS is not None:
+        enable_counters(True)
+
+
+def counters():
+    """Counts since the last reset: sim1_solver -- levels whose new thickness took the p_fac pressure floor / did not; update_dz_c /
+    update_dz_d -- interface heights the dz_min scan raised / left; update_dz_c -- interface fluxes that took the upwind value from
+    the cell behind (flux > 0) / ahead, in x and in y; apply_diffusive_heating -- cells whose temperature change was cut to the
+    limit / was not; ray_fast -- levels (per call) that are damped / only receive the momentum fix / neither."""
+    return dict(_COUNTS or dict.fromkeys(COUNTERS, 0))
+
+
+def _count(name, mask):
+    if _COUNTS is not None:
+        _COUNTS[name] += int(np.count_nonzero(mask))
+
+
+def _count2(yes, no, mask):
+    if _COUNTS is not None:
+        n = int(np.count_nonzero(mask))
+        _COUNTS[yes] += n
+        _COUNTS[no] += int(np.size(mask)) - n
+
 
 # ---------------------------------------------------------------------------
 # update_dz_c  [SURVEY A.5]
@@ -44,9 +80,11 @@ def update_dz_c(D: Dom, dp_ref, zs, ut, vt, gz, ws, dt):
     fy = np.zeros_like(gz)
     Rm = S(is_ - 2, ie + 1, js - 1, je + 1)
     fx[Rx] = xfx[Rx] * np.where(xfx[Rx] > 0.0, gz2[Rm], gz2[Rx])
+    _count2("dzc_upwind_pos_x", "dzc_upwind_neg_x", xfx[Rx] > 0.0)
     fill_4corners(D, gz2, 2)
     Rm = S(is_ - 1, ie + 1, js - 2, je + 1)
     fy[Ry] = yfx[Ry] * np.where(yfx[Ry] > 0.0, gz2[Rm], gz2[Ry])
+    _count2("dzc_upwind_pos_y", "dzc_upwind_neg_y", yfx[Ry] > 0.0)
     R = S(is_ - 1, ie + 1, js - 1, je + 1)
     Rxp = S(is_, ie + 2, js - 1, je + 1)
     Ryp = S(is_ - 1, ie + 1, js, je + 2)
@@ -54,6 +92,7 @@ def update_dz_c(D: Dom, dp_ref, zs, ut, vt, gz, ws, dt):
     ws[R] = (zs[R] - gz[R + (slice(nz, nz + 1),)]) / dt
     g = gz[R]
     for k in range(nz - 1, -1, -1):
+        _count2("dzc_limited", "dzc_free", g[:, :, k] < g[:, :, k + 1] + dz_min)
         g[:, :, k] = np.maximum(g[:, :, k], g[:, :, k + 1] + dz_min)
     gz[R] = g
 
@@ -140,6 +179,7 @@ def update_dz_d(D: Dom, cfg, col, dp_ref, zs, zh, crx, cry, xfx, yfx, ws, dt):
     ws[Rc] = (zs[Rc] - zh[Rc + (slice(nz, nz + 1),)]) / dt
     g = zh[Rc]
     for k in range(nz - 1, -1, -1):
+        _count2("dzd_limited", "dzd_free", g[:, :, k] < g[:, :, k + 1] + dz_min)
         g[:, :, k] = np.maximum(g[:, :, k], g[:, :, k + 1] + dz_min)
     zh[Rc] = g
 
@@ -149,7 +189,11 @@ def update_dz_d(D: Dom, cfg, col, dp_ref, zs, zh, crx, cry, xfx, yfx, ws, dt):
 # ---------------------------------------------------------------------------
 def sim1_solver(c, dt, gm, cp2, pe, dm, pm, pem, w, dz, pt, ws, p_fac):
     """FV3 SIM1_solver (MOIST_CAPPA form) on columns [..., k].  w, dz, pe updated in place.
-    pe: [..., nz+1] work/output (non-hydrostatic pressure perturbation)."""
+    pe: [..., nz+1] work/output (non-hydrostatic pressure perturbation).  Every work array takes the dtype of dm, so np.longdouble
+    inputs give a high-precision solve (how the tests measure the fp64 round-off of a badly conditioned column).  The scalar constants
+    (1/3, 2 dt^2, 1/dt, rgas, and akap / rgrav in the callers) stay Python doubles in that mode: it removes the round-off of the
+    operations on the arrays, not the fp64 rounding of those constants, which both solves share -- a figure measured against it is a
+    lower estimate of the fp64 solve's error."""
     nz = w.shape[-1]
     rgas = c.RDGAS
     t1g = 2.0 * dt * dt
@@ -164,7 +208,7 @@ def sim1_solver(c, dt, gm, cp2, pe, dm, pm, pem, w, dz, pt, ws, p_fac):
     dd[..., :-1] = 3.0 * (pe1[..., :-1] + g_rat * pe1[..., 1:])
     bb[..., nz - 1] = 2.0
     dd[..., nz - 1] = 3.0 * pe1[..., nz - 1]
-    pp = np.zeros(dm.shape[:-1] + (nz + 1,))
+    pp = np.zeros(dm.shape[:-1] + (nz + 1,), dtype=dm.dtype)
     gam = np.zeros_like(dm)
     bet = bb[..., 0].copy()
     pp[..., 1] = dd[..., 0] / bet
@@ -192,9 +236,11 @@ def sim1_solver(c, dt, gm, cp2, pe, dm, pm, pem, w, dz, pt, ws, p_fac):
     for k in range(nz):
         pe[..., k + 1] = pe[..., k] + dm[..., k] * (w[..., k] - w1[..., k]) * rdt
     p1 = (pe[..., nz - 1] + 2.0 * pe[..., nz]) * r3
+    _count2("sim1_floor", "sim1_free", p_fac * pm[..., nz - 1] > p1 + pm[..., nz - 1])
     dz[..., nz - 1] = -dm[..., nz - 1] * rgas * pt[..., nz - 1] * np.exp((cp2[..., nz - 1] - 1.0) * np.log(np.maximum(p_fac * pm[..., nz - 1], p1 + pm[..., nz - 1])))
     for k in range(nz - 2, -1, -1):
         p1 = (pe[..., k] + bb[..., k] * pe[..., k + 1] + g_rat[..., k] * pe[..., k + 2]) * r3 - g_rat[..., k] * p1
+        _count2("sim1_floor", "sim1_free", p_fac * pm[..., k] > p1 + pm[..., k])
         dz[..., k] = -dm[..., k] * rgas * pt[..., k] * np.exp((cp2[..., k] - 1.0) * np.log(np.maximum(p_fac * pm[..., k], p1 + pm[..., k])))
 
 
@@ -209,8 +255,8 @@ def riem_solver_c(D: Dom, dt2, cappa, ptop, phis, ws, ptc, q_con, delpc, gz, pef
     cp2 = cappa[R][:, :, :nz]
     qc = q_con[R][:, :, :nz]
     shp = dm.shape[:2] + (nz + 1,)
-    pem = np.zeros(shp)
-    peg = np.zeros(shp)
+    pem = np.zeros(shp, dtype=dm.dtype)
+    peg = np.zeros(shp, dtype=dm.dtype)
     pem[..., 0] = ptop
     peg[..., 0] = ptop
     for k in range(nz):
@@ -222,12 +268,12 @@ def riem_solver_c(D: Dom, dt2, cappa, ptop, phis, ws, ptc, q_con, delpc, gz, pef
     gm2 = 1.0 / (1.0 - cp2)
     dm = dm * c.RGRAV
     w2 = w3[R][:, :, :nz].copy()
-    pe2 = np.zeros(shp)
+    pe2 = np.zeros(shp, dtype=dm.dtype)
     sim1_solver(c, dt2, gm2, cp2, pe2, dm, pm2, pem, w2, dz2, ptc[R][:, :, :nz], ws[R][:, :, 0], p_fac)
     out = pe2 + pem
     out[..., 0] = ptop
     pef[R] = out
-    g = np.zeros(shp)
+    g = np.zeros(shp, dtype=dm.dtype)
     g[..., nz] = phis[R][:, :, 0]
     for k in range(nz - 1, -1, -1):
         g[..., k] = g[..., k + 1] - dz2[..., k] * c.GRAV
@@ -246,8 +292,8 @@ def riem_solver3(D: Dom, last_call, dt, cappa, ptop, zs, ws, delz, q_con, delp, 
     cp2 = cappa[R][:, :, :nz]
     qc = q_con[R][:, :, :nz]
     shp = dm.shape[:2] + (nz + 1,)
-    pem = np.zeros(shp)
-    peg = np.zeros(shp)
+    pem = np.zeros(shp, dtype=dm.dtype)
+    peg = np.zeros(shp, dtype=dm.dtype)
     pem[..., 0] = ptop
     peg[..., 0] = ptop
     for k in range(nz):
@@ -262,7 +308,7 @@ def riem_solver3(D: Dom, last_call, dt, cappa, ptop, zs, ws, delz, q_con, delp, 
     z = zh[R]
     dz2 = z[..., 1:] - z[..., :-1]
     w2 = w[R][:, :, :nz].copy()
-    pe2 = np.zeros(shp)
+    pe2 = np.zeros(shp, dtype=dm.dtype)
     sim1_solver(c, dt, gm2, cp2, pe2, dm, pm2, pem, w2, dz2, pt[R][:, :, :nz], ws[R][:, :, 0], p_fac)
     w[R + (slice(0, nz),)] = w2
     delz[R + (slice(0, nz),)] = dz2
@@ -272,7 +318,7 @@ def riem_solver3(D: Dom, last_call, dt, cappa, ptop, zs, ws, delz, q_con, delp, 
         pk[R] = pk3v
         pe[R] = pem
     ppe[R] = pe2
-    znew = np.zeros(shp)
+    znew = np.zeros(shp, dtype=dm.dtype)
     znew[..., nz] = zs[R][:, :, 0]
     for k in range(nz - 1, -1, -1):
         znew[..., k] = znew[..., k + 1] - dz2[..., k]
@@ -396,6 +442,9 @@ def ray_fast(D: Dom, cfg, u, v, w, dp, pfull, dt, ptop):
     rf = np.ones(nz)
     rfv = dt / tau0 * np.sin(0.5 * c.PI * np.log(rf_cutoff / pfull[damped]) / np.log(rf_cutoff / ptop)) ** 2
     rf[damped] = 1.0 / (1.0 + rfv)
+    _count("ray_damped", damped)
+    _count("ray_nudged_only", nudged & ~damped)
+    _count("ray_none", ~nudged)
     if not nudged.any():
         return
     dm = np.sum(dp[nudged])
@@ -465,4 +514,5 @@ def apply_diffusive_heating(D: Dom, delp, delz, cappa, heat_source, pt, delt_tim
     lim[0] *= 0.1
     if nz > 1:
         lim[1] *= 0.5
+    _count2("heat_limited", "heat_free", np.abs(dtmp) > lim)
     pt[R] = pt[R] + np.sign(dtmp) * np.minimum(lim, np.abs(dtmp)) / pkz

@@ -79,8 +79,8 @@ def recorded(layout, nz=8):
 class Dev:
     """All ranks of the cube in one device context; Quantities from lists of per-rank oracle arrays."""
 
-    def __init__(self, backend, grids, cfg):
-        self.sf = stencil_factory_for(backend)(grids, cfg, get_constants())
+    def __init__(self, backend, grids, cfg, constants=None, dtype=torch.float64):
+        self.sf = stencil_factory_for(backend)(grids, cfg, constants or get_constants(), dtype=dtype)
         self.qf = self.sf.quantity_factory
         self.nz = grids[0].nz
 
