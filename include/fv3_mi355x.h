@@ -365,6 +365,22 @@ int fv3_remap(fv3_ctx *, int n_tracers, const fv3_field *const *tracers, const f
 int fv3_cubed_to_latlon(fv3_ctx *, int order, const fv3_field *u, const fv3_field *v, const fv3_field *ua, const fv3_field *va,
                         const fv3_field *a11, const fv3_field *a12, const fv3_field *a21, const fv3_field *a22, void *stream);
 
+/* ---- driver diagnostics (fv3_diag.hip): what the driver stores every output_frequency steps ------------------------------
+ * [REF driver/pace/driver/diagnostics.py].  Neither entry allocates: the caller owns `out`, a contiguous device array in the
+ * build's Real.  Neither reads a halo cell or the pad level.
+ *
+ * fv3_diag_pack: the compute box i = 1..ni, j = 1..nj, levels k0 .. k0+nk-1 of every sub-domain of `src` -> out[t][k][j][i]
+ * (i fastest).  ni is nx or nx+1, nj is ny or ny+1 (the staggered end belongs to the variable: u has nj = ny+1, v ni = nx+1);
+ * the level range lies in [0, nz] for a 3-D field (an interface field: nk = nz+1), a 2-D field (shape[2] == 1) takes k0 = 0,
+ * nk = 1; a level slice is nk = 1.  A null out, another ni / nj, a level range outside the field or
+ * out_elems != n_sub * nk * nj * ni: FV3_ERR_ARG, a message, nothing launched.  One launch for all sub-domains. */
+int fv3_diag_pack(fv3_ctx *, const fv3_field *src, int ni, int nj, int k0, int nk, void *out, long out_elems, void *stream);
+
+/* fv3_diag_column_integral: out[t][j][i] = rgrav * sum_{k = 0}^{nz-1} q * delp on the compute cells (rgrav = 1 / grav of the
+ * context's constants; kg/m^2 for a mixing ratio).  The products are rounded, then added in increasing k in Real, the sum is
+ * multiplied by rgrav once: the result is fixed bitwise.  out_elems must be n_sub * ny * nx. */
+int fv3_diag_column_integral(fv3_ctx *, const fv3_field *q, const fv3_field *delp, void *out, long out_elems, void *stream);
+
 /* ---- per-operator timing (HIP events on the operators' stream) --------------------------------- */
 enum fv3_op {
   FV3_OP_C_SW = 0,

@@ -20,6 +20,13 @@ dycore_config.*`` (the fields of ``AcousticDynamicsConfig``), ``stencil_config.c
 recipe of SURVEY §8d; the analytic baroclinic state is not part of this build and the driver says
 so).  ``backend`` values other than ``hip:gfx950`` are reported and replaced: this build has one
 backend.  Multi-process runs take RANK / WORLD_SIZE / LOCAL_RANK from the environment like bench.py.
+
+Diagnostics [REF driver/pace/driver/driver.py:551-552, 588-611, 702-705]: with a ``diagnostics_config`` block in the yaml
+(``pace_amd.diagnostics.DiagnosticsConfig``) the driver stores the initial state when ``output_initial_state`` is set, stores after
+every ``output_frequency``-th step -- outside the step clock -- and ends with ``store_grid`` and ``cleanup``.  Names of the block that
+this build's state does not hold (``qvapor`` ... ``qgraupel``, ``ps``: the reference's yamls ask for them) are dropped and reported in
+one line.  ``--diagnostics-path DIR`` overrides the block's ``path``, ``--no-diagnostics`` turns the block off.  Without a block
+nothing changes.
 """
 from __future__ import annotations
 
@@ -57,8 +64,43 @@ def load_config(path: str):
         dycore_only=bool(y.get("dycore_only", False)),
         disable_step_physics=bool(y.get("disable_step_physics", False)),
         experiment=((y.get("performance_config") or {}).get("experiment_name", os.path.splitext(os.path.basename(path))[0])),
+        # diagnostics [REF driver/pace/driver/driver.py:88-93, 132-133; initialization.config.start_time, default 2000-01-01]
+        diagnostics_config=y.get("diagnostics_config") or None,
+        output_initial_state=bool(y.get("output_initial_state", False)),
+        output_frequency=int(y.get("output_frequency", 1)),
+        start_time=(((y.get("initialization") or {}).get("config") or {}).get("start_time", None)),
     )
     return run, dy, ignored
+
+
+def filter_diagnostics(block, known):
+    """The yaml's ``diagnostics_config`` block without the names this build's state does not hold (``known``: state fields + tracers):
+    (block, dropped names).  ``column_integrated_<tracer>`` is dropped with its tracer; other derived names are left to the diagnostics
+    (they warn, like the reference's)."""
+    from .diagnostics import COLUMN_INTEGRATED
+
+    block = dict(block or {})
+    known = set(known)
+    dropped = []
+
+    def keep(names, is_known=lambda n: n in known):
+        out = []
+        for n in names or []:
+            (out if is_known(n) else dropped).append(n)
+        return out
+
+    if "names" in block:
+        block["names"] = keep(block["names"])
+    if "derived_names" in block:
+        block["derived_names"] = keep(block["derived_names"], lambda n: not n.startswith(COLUMN_INTEGRATED) or n[len(COLUMN_INTEGRATED):] in known)
+    if "z_select" in block:
+        zs = []
+        for z in block["z_select"] or []:
+            names = keep(z["names"])
+            if names:
+                zs.append({"level": z["level"], "names": names})
+        block["z_select"] = zs
+    return block, dropped
 
 
 def main(argv=None):
@@ -73,6 +115,8 @@ def main(argv=None):
     ap.add_argument("--remap", action="store_true", help="Lagrangian-to-Eulerian remap after every acoustic call (with --tracers: the body of DynamicalCore.step_dynamics)")
     ap.add_argument("--latlon-winds", action="store_true",
                     help="CubedToLatLon at the end of every step (c2l_ord from the yaml, default 4): state ua / va become the eastward / northward cell-centre winds")
+    ap.add_argument("--diagnostics-path", default=None, help="directory of the diagnostics (overrides diagnostics_config.path of the yaml)")
+    ap.add_argument("--no-diagnostics", action="store_true", help="ignore the yaml's diagnostics_config block")
     a = ap.parse_args(argv)
     run, dy, ignored = load_config(a.config)
 
@@ -121,6 +165,29 @@ def main(argv=None):
         h.dyn._bind(h.state)
         say(f"state loaded from {a.restart}")
     n_steps = a.steps or run["n_steps"]
+    # diagnostics: built after the harness (the reference's order), bound to its state, tracers, layout and stencil factory
+    from .diagnostics import DiagnosticsConfig, NullDiagnostics
+    from .dyn_core import STATE_NAMES
+
+    diagnostics = NullDiagnostics()
+    if run["diagnostics_config"] and not a.no_diagnostics:
+        block, dropped = filter_diagnostics(run["diagnostics_config"], STATE_NAMES + ["phis"] + list(h.tracers))
+        if a.diagnostics_path:
+            block["path"] = a.diagnostics_path
+        if dropped:
+            say("diagnostics: this build's state does not hold " + ", ".join(dropped) + " -- dropped from the output")
+        dcfg = DiagnosticsConfig.from_dict(block)
+        diagnostics = dcfg.diagnostics_factory(h, start_time=run["start_time"])
+        if dcfg.path is not None:
+            say(f"diagnostics: {dcfg.output_format} -> {dcfg.path}: {', '.join(diagnostics.variables)}; every {run['output_frequency']} step(s)"
+                + (", initial state included" if run["output_initial_state"] else ""))
+    from datetime import timedelta
+
+    from .monitor import as_datetime
+
+    start_time = as_datetime(run["start_time"])
+    if run["output_initial_state"]:
+        diagnostics.store(start_time)
     from .timer import Timer
 
     # The reference's timestep timer: one "mainloop" entry per model step [REF driver/pace/driver/driver.py:640], and inside it the
@@ -140,8 +207,12 @@ def main(argv=None):
             h.step(timer)  # dycore.step_dynamics for dycore_only + disable_step_physics
         times_per_step.append(timer.times)
         hits_per_step.append(timer.hits)
+        if (step + 1) % run["output_frequency"] == 0:  # (outside the step clock)
+            diagnostics.store(start_time + timedelta(seconds=(step + 1) * run["dt_atmos"]))
     times = [t[loop_name] for t in times_per_step]
     ok = all(v[2] for v in h.sanity().values())
+    diagnostics.store_grid(h.grids)
+    diagnostics.cleanup()
     if a.save_restart:
         from . import restart
 

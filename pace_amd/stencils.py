@@ -315,3 +315,79 @@ class CubedToLatLon(_Op):
         if self.order == 4:
             self._uv_updater(u, v).update()  # mpp_update_domains(u, v, DGRID_NE) inside c2l_ord4
         self.sf.call("cubed_to_latlon", self.order, u.fref, v.fref, ua.fref, va.fref, self.a11.fref, self.a12.fref, self.a21.fref, self.a22.fref)
+
+
+def _box_extent(sf, q: Quantity, op: str):
+    """(ni, nj, nk) of the compute box of ``q`` from its dims: ``x_interface`` / ``y_interface`` / ``z_interface`` add one; nk is
+    None for a 2-D quantity."""
+    s = sf.sizer
+    if len(q.dims) < 2 or q.dims[0] not in (X_DIM, X_INTERFACE_DIM) or q.dims[1] not in (Y_DIM, Y_INTERFACE_DIM):
+        raise ValueError(f"{op}: dims {q.dims} (the first two must be x | x_interface, y | y_interface)")
+    ni = s.nx + (1 if q.dims[0] == X_INTERFACE_DIM else 0)
+    nj = s.ny + (1 if q.dims[1] == Y_INTERFACE_DIM else 0)
+    if len(q.dims) == 2:
+        if not q.is_2d:
+            raise ValueError(f"{op}: dims {q.dims} on a 3-D storage")
+        return ni, nj, None
+    if q.is_2d or q.dims[2] not in (Z_DIM, Z_INTERFACE_DIM):
+        raise ValueError(f"{op}: dims {q.dims} (the third must be z | z_interface, on a 3-D storage)")
+    return ni, nj, s.nz + (1 if q.dims[2] == Z_INTERFACE_DIM else 0)
+
+
+def _out_ptr(sf, out, n: int, op: str):
+    """Device pointer of the caller's output buffer (a contiguous torch tensor of the context's dtype and device, at least n elements)."""
+    if out.dtype != sf.dtype or out.device.type != sf.device.type or not out.is_contiguous():
+        raise ValueError(f"{op}: out must be a contiguous {sf.dtype} tensor on {sf.device}")
+    if out.numel() < n:
+        raise ValueError(f"{op}: out holds {out.numel()} elements, {n} are needed")
+    return out.data_ptr()
+
+
+class FieldPack(_Op):
+    """The compute domain of a Quantity, packed on the device into ``out[n_sub, (nk,) nj, ni]`` (i fastest) -- what the driver's
+    diagnostics move to the host instead of the padded storage (``fv3_diag_pack``).  The box follows the Quantity's dims
+    (``x_interface`` / ``y_interface`` / ``z_interface`` add one); ``level`` packs that single level of a 3-D quantity as a 2-D
+    array.  ``out`` is the caller's buffer (a contiguous device tensor with room for the box; nothing is allocated); the
+    call returns the view of ``out`` with the packed shape."""
+
+    def shape(self, q: Quantity, level: Optional[int] = None):
+        ni, nj, nk = _box_extent(self.sf, q, "FieldPack")
+        if nk is None:
+            if level is not None:
+                raise ValueError("FieldPack: level given for a 2-D quantity")
+            return (q.n_sub, nj, ni)
+        if level is not None:
+            if not 0 <= int(level) < nk:
+                raise ValueError(f"FieldPack: level {level} outside [0, {nk}) of dims {q.dims}")
+            return (q.n_sub, nj, ni)
+        return (q.n_sub, nk, nj, ni)
+
+    def __call__(self, q: Quantity, out, level: Optional[int] = None):
+        shape = self.shape(q, level)
+        ni, nj = shape[-1], shape[-2]
+        k0, nk = (0, shape[1]) if len(shape) == 4 else (int(level or 0), 1)
+        n = 1
+        for e in shape:
+            n *= e
+        self.sf.call("diag_pack", q.fref, ni, nj, k0, nk, _out_ptr(self.sf, out, n, "FieldPack"), n)
+        return out.view(-1)[:n].view(shape)
+
+
+class ColumnIntegral(_Op):
+    """``rgrav * sum_k q * delp`` on the compute cells (``fv3_diag_column_integral``; the reference driver's
+    ``column_integrated_<tracer>`` [REF driver/pace/driver/diagnostics.py:226-249], kg/m**2), into ``out[n_sub, ny, nx]`` of the
+    caller's buffer; returns that view."""
+
+    units = "kg/m**2"
+
+    def shape(self, q: Quantity):
+        if tuple(q.dims) != _CELL:
+            raise NotImplementedError(f"ColumnIntegral: dims {q.dims} (a cell-centre quantity (x, y, z) is expected)")
+        return (q.n_sub, self.sf.sizer.ny, self.sf.sizer.nx)
+
+    def __call__(self, q: Quantity, delp: Quantity, out):
+        shape = self.shape(q)
+        self.shape(delp)
+        n = shape[0] * shape[1] * shape[2]
+        self.sf.call("diag_column_integral", q.fref, delp.fref, _out_ptr(self.sf, out, n, "ColumnIntegral"), n)
+        return out.view(-1)[:n].view(shape)
