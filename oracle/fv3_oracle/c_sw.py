@@ -16,6 +16,42 @@ C2 = 11.0 / 14.0
 C3 = 5.0 / 14.0
 BIG = 1.0e30
 
+# Opt-in branch counters for the tests (the interface of fv3_oracle.ppm / fv3_oracle.nh): number of evaluated points that took each
+# side of a switch.  None = off (the default); counting never changes a value.
+_COUNTS = None
+COUNTERS = tuple(
+    [f"{f}_{sg}" for f in ("uc_w", "uc_e", "vc_s", "vc_n", "ke_w", "ke_e", "vort_s", "vort_n", "flux_x", "flux_y", "fyv", "fxv") for sg in ("pos", "neg")]
+)
+
+
+def enable_counters(on: bool = True) -> None:
+    global _COUNTS
+    _COUNTS = dict.fromkeys(COUNTERS, 0) if on else None
+
+
+def reset_counters() -> None:
+    if _COUNTS is not None:
+        enable_counters(True)
+
+
+def counters():
+    """Counts since the last reset.  uc_<w|e> / vc_<s|n>: the tile-edge column / row of the C-grid wind, contravariant wind > 0 (the
+    metric of the cell before the edge) or not; ke_<w|e> / vort_<s|n>: the two cells either side of a tile edge -- _pos the cell after
+    the edge with its wind > 0, _neg the cell before it with its wind <= 0: the two cells that take the edge projection; flux_x /
+    flux_y: the first-order upwind fluxes of delp / pt / w; fyv / fxv: the upwind corner of the vorticity fluxes."""
+    return dict(_COUNTS or dict.fromkeys(COUNTERS, 0))
+
+
+def _count(name, mask):
+    if _COUNTS is not None:
+        _COUNTS[name] += int(np.count_nonzero(mask))
+
+
+def _count_sign(name, pos):
+    if _COUNTS is not None:
+        _count(name + "_pos", pos)
+        _count(name + "_neg", ~pos)
+
 
 def _edge_interpolate4(ua, dxa):
     """ua, dxa: lists of 4 consecutive cells straddling the edge (2 outside, 2 inside)."""
@@ -119,6 +155,7 @@ def d2a2c_vect(D: Dom, u, v, ua, va, uc, vc, ut, vt):
         setcol(uc, 0, C1 * col(utmp, -2) + C2 * col(utmp, -1) + C3 * col(utmp, 0))
         ut1 = _edge_interpolate4([col(ua, i) for i in (-1, 0, 1, 2)], [col(m.dxa, i) for i in (-1, 0, 1, 2)])
         setcol(ut, 1, ut1)
+        _count_sign("uc_w", ut1 > 0.0)
         setcol(uc, 1, np.where(ut1 > 0.0, ut1 * col(m.sin_sg3, 0), ut1 * col(m.sin_sg1, 1)))
         setcol(uc, 2, C1 * col(utmp, 3) + C2 * col(utmp, 2) + C3 * col(utmp, 1))
         setcol(ut, 0, (col(uc, 0) - col(v, 0) * col(m.cosa_u, 0)) * col(m.rsin_u, 0))
@@ -127,6 +164,7 @@ def d2a2c_vect(D: Dom, u, v, ua, va, uc, vc, ut, vt):
         setcol(uc, npx - 1, C1 * col(utmp, npx - 3) + C2 * col(utmp, npx - 2) + C3 * col(utmp, npx - 1))
         utn = _edge_interpolate4([col(ua, i) for i in (npx - 2, npx - 1, npx, npx + 1)], [col(m.dxa, i) for i in (npx - 2, npx - 1, npx, npx + 1)])
         setcol(ut, npx, utn)
+        _count_sign("uc_e", utn > 0.0)
         setcol(uc, npx, np.where(utn > 0.0, utn * col(m.sin_sg3, npx - 1), utn * col(m.sin_sg1, npx)))
         setcol(uc, npx + 1, C3 * col(utmp, npx) + C2 * col(utmp, npx + 1) + C1 * col(utmp, npx + 2))
         setcol(ut, npx - 1, (col(uc, npx - 1) - col(v, npx - 1) * col(m.cosa_u, npx - 1)) * col(m.rsin_u, npx - 1))
@@ -175,6 +213,7 @@ def d2a2c_vect(D: Dom, u, v, ua, va, uc, vc, ut, vt):
     if Sd:
         vt1 = _edge_interpolate4([row(va, j) for j in (-1, 0, 1, 2)], [row(m.dya, j) for j in (-1, 0, 1, 2)])
         setrow(vt, 1, vt1)
+        _count_sign("vc_s", vt1 > 0.0)
         setrow(vc, 1, np.where(vt1 > 0.0, vt1 * row(m.sin_sg4, 0), vt1 * row(m.sin_sg2, 1)))
         setrow(vc, 0, C1 * row(vtmp, -2) + C2 * row(vtmp, -1) + C3 * row(vtmp, 0))
         setrow(vt, 0, (row(vc, 0) - row(u, 0) * row(m.cosa_v, 0)) * row(m.rsin_v, 0))
@@ -183,6 +222,7 @@ def d2a2c_vect(D: Dom, u, v, ua, va, uc, vc, ut, vt):
     if N:
         vtn = _edge_interpolate4([row(va, j) for j in (npy - 2, npy - 1, npy, npy + 1)], [row(m.dya, j) for j in (npy - 2, npy - 1, npy, npy + 1)])
         setrow(vt, npy, vtn)
+        _count_sign("vc_n", vtn > 0.0)
         setrow(vc, npy, np.where(vtn > 0.0, vtn * row(m.sin_sg4, npy - 1), vtn * row(m.sin_sg2, npy)))
         setrow(vc, npy - 1, C1 * row(vtmp, npy - 3) + C2 * row(vtmp, npy - 2) + C3 * row(vtmp, npy - 1))
         setrow(vt, npy - 1, (row(vc, npy - 1) - row(u, npy - 1) * row(m.cosa_v, npy - 1)) * row(m.rsin_v, npy - 1))
@@ -255,6 +295,7 @@ def c_sw(D: Dom, delp, pt, u, v, w, uc, vc, ua, va, ut, vt, divgd, omga, dt2, no
     R = S(is_ - 1, ie + 2, js - 1, je + 1)
     Rm = S(is_ - 2, ie + 1, js - 1, je + 1)
     pos = ut[R] > 0.0
+    _count_sign("flux_x", pos)
     fx1 = np.zeros_like(delp)
     fx = np.zeros_like(delp)
     fx2 = np.zeros_like(delp)
@@ -266,6 +307,7 @@ def c_sw(D: Dom, delp, pt, u, v, w, uc, vc, ua, va, ut, vt, divgd, omga, dt2, no
     R = S(is_ - 1, ie + 1, js - 1, je + 2)
     Rm = S(is_ - 1, ie + 1, js - 2, je + 1)
     pos = vt[R] > 0.0
+    _count_sign("flux_y", pos)
     fy1 = np.zeros_like(delp)
     fy = np.zeros_like(delp)
     fy2 = np.zeros_like(delp)
@@ -287,17 +329,21 @@ def c_sw(D: Dom, delp, pt, u, v, w, uc, vc, ua, va, ut, vt, divgd, omga, dt2, no
     ke[R] = np.where(ua[R] > 0.0, uc[R], uc[Rx])
     vort[R] = np.where(va[R] > 0.0, vc[R], vc[Ry])
     # tile-edge cells: project with the edge metric (FV3 sw_corrected branch)
-    for flag, iw, ie_ in ((D.west, 1, 0), (D.east, npx, npx - 1)):
+    for flag, iw, ie_, edge in ((D.west, 1, 0, "w"), (D.east, npx, npx - 1, "e")):
         if flag:
             # ua > 0 at cell iw (upwind face i=iw) ; ua <= 0 at cell ie_ (face i=ie_+1)
             Rc = S(iw, iw, js - 1, je + 1)
+            _count(f"ke_{edge}_pos", ua[Rc] > 0.0)
+            _count(f"ke_{edge}_neg", ~(ua[S(ie_, ie_, js - 1, je + 1)] > 0.0))
             ke[Rc] = np.where(ua[Rc] > 0.0, uc[Rc] * m.sin_sg1[Rc] + v[Rc] * m.cos_sg1[Rc], ke[Rc])
             Rc = S(ie_, ie_, js - 1, je + 1)
             Rp = S(ie_ + 1, ie_ + 1, js - 1, je + 1)
             ke[Rc] = np.where(ua[Rc] > 0.0, ke[Rc], uc[Rp] * m.sin_sg3[Rc] + v[Rp] * m.cos_sg3[Rc])
-    for flag, jw, je_ in ((D.south, 1, 0), (D.north, npy, npy - 1)):
+    for flag, jw, je_, edge in ((D.south, 1, 0, "s"), (D.north, npy, npy - 1, "n")):
         if flag:
             Rc = S(is_ - 1, ie + 1, jw, jw)
+            _count(f"vort_{edge}_pos", va[Rc] > 0.0)
+            _count(f"vort_{edge}_neg", ~(va[S(is_ - 1, ie + 1, je_, je_)] > 0.0))
             vort[Rc] = np.where(va[Rc] > 0.0, vc[Rc] * m.sin_sg2[Rc] + u[Rc] * m.cos_sg2[Rc], vort[Rc])
             Rc = S(is_ - 1, ie + 1, je_, je_)
             Rp = S(is_ - 1, ie + 1, je_ + 1, je_ + 1)
@@ -332,6 +378,7 @@ def c_sw(D: Dom, delp, pt, u, v, w, uc, vc, ua, va, ut, vt, divgd, omga, dt2, no
         if flag:
             Rc = S(i, i, js, je)
             fy1f[Rc] = dt2 * v[Rc]
+    _count_sign("fyv", fy1f[Ru] > 0.0)
     fyv = np.where(fy1f[Ru] > 0.0, vort[Ru], vort[S(is_, ie + 1, js + 1, je + 1)])
     uc[Ru] = uc[Ru] + fy1f[Ru] * fyv + m.rdxc[Ru] * (ke[S(is_ - 1, ie, js, je)] - ke[Ru])
     Rvv = S(is_, ie, js, je + 1)
@@ -341,6 +388,7 @@ def c_sw(D: Dom, delp, pt, u, v, w, uc, vc, ua, va, ut, vt, divgd, omga, dt2, no
         if flag:
             Rc = S(is_, ie, j, j)
             fx1f[Rc] = dt2 * u[Rc]
+    _count_sign("fxv", fx1f[Rvv] > 0.0)
     fxv = np.where(fx1f[Rvv] > 0.0, vort[Rvv], vort[S(is_ + 1, ie + 1, js, je + 1)])
     vc[Rvv] = vc[Rvv] - fx1f[Rvv] * fxv + m.rdyc[Rvv] * (ke[S(is_, ie, js - 1, je)] - ke[Rvv])
     return delpc, ptc

@@ -18,6 +18,56 @@ from .ppm import xtp_u, ytp_v
 from .util import Dom, fill_corners_bgrid, fill_corners_dgrid_vector
 
 
+# Opt-in branch counters for the tests (the interface of fv3_oracle.ppm / fv3_oracle.nh): number of evaluated points that took each
+# side of a switch.  None = off (the default); counting never changes a value.
+_COUNTS = None
+COUNTERS = tuple(
+    [f"damp{form}_{side}" for form in ("0", "n") for side in ("capped", "floored", "free")]
+    + [f"fxadv_{e}_{sg}" for e in ("ut_w", "ut_e", "vt_s", "vt_n") for sg in ("pos", "neg")]
+    + [f"div0_{e}_{sg}" for e in ("ptc_s", "ptc_n", "vort_w", "vort_e") for sg in ("pos", "neg")]
+    + [f"{name}_{side}" for name in ("d_con", "damp_w", "damp_vt") for side in ("on", "off")]
+)
+
+
+def enable_counters(on: bool = True) -> None:
+    global _COUNTS
+    _COUNTS = dict.fromkeys(COUNTERS, 0) if on else None
+
+
+def reset_counters() -> None:
+    if _COUNTS is not None:
+        enable_counters(True)
+
+
+def counters():
+    """Counts since the last reset.  damp0_* / dampn_*: corners of the nord == 0 / the higher-order divergence damping whose
+    coefficient da_min_c * max(d2_bg, min(0.20, x)) is floored (d2_bg >= min(0.20, x): the background wins), capped (x > 0.20 above
+    the background) or free (x itself); fxadv_<ut_w|ut_e|vt_s|vt_n>_<pos|neg>: the upwind metric of the contravariant wind on a tile
+    edge (dt * wind > 0 or not), over the whole edge line; div0_<ptc_s|ptc_n|vort_w|vort_e>_*: the same choice in the tile-edge rows /
+    columns of the nord == 0 divergence; d_con / damp_w / damp_vt _on / _off: level groups (one count per group of a call, not per
+    point) with the parameter above / not above its 1e-5 threshold."""
+    return dict(_COUNTS or dict.fromkeys(COUNTERS, 0))
+
+
+def _count(name, mask):
+    if _COUNTS is not None:
+        _COUNTS[name] += int(np.count_nonzero(mask))
+
+
+def _count_sign(name, pos):
+    if _COUNTS is not None:
+        _count(name + "_pos", pos)
+        _count(name + "_neg", ~pos)
+
+
+def _count_damp(form, d2_bg, x):
+    if _COUNTS is not None:
+        floored = d2_bg >= np.minimum(0.20, x)
+        _count(f"damp{form}_floored", floored)
+        _count(f"damp{form}_capped", ~floored & (x > 0.20))
+        _count(f"damp{form}_free", ~floored & ~(x > 0.20))
+
+
 # ---------------------------------------------------------------------------
 # per-level parameters  [SURVEY A.3.9; pyFV3 d_sw.get_column_namelist]
 # ---------------------------------------------------------------------------
@@ -162,9 +212,10 @@ def fxadv(D: Dom, uc, vc, crx, cry, xfx, yfx, ut, vt, dt):
     def row(a, j, i0=isd, i1=ied):
         return a[i0 + o : i1 + o + 1, j + o : j + o + 1]
 
-    for flag, i in ((W, 1), (E, npx)):
+    for flag, i, edge in ((W, 1, "w"), (E, npx, "e")):
         if flag:
             ucol = col(uc, i)
+            _count_sign("fxadv_ut_" + edge, ucol * dt > 0.0)
             ut[i + o : i + o + 1, jsd + o : jed + o + 1] = np.where(ucol * dt > 0.0, ucol / col(m.sin_sg3, i - 1), ucol / col(m.sin_sg1, i))
             j0, j1 = max(3, js), min(npy - 2, je + 1)
             if not Sd:
@@ -175,9 +226,10 @@ def fxadv(D: Dom, uc, vc, crx, cry, xfx, yfx, ut, vt, dt):
                 vt[iv + o : iv + o + 1, j0 + o : j1 + o + 1] = col(vc, iv, j0, j1) - 0.25 * col(m.cosa_v, iv, j0, j1) * (
                     col(ut, iv, j0 - 1, j1 - 1) + col(ut, iv + 1, j0 - 1, j1 - 1) + col(ut, iv, j0, j1) + col(ut, iv + 1, j0, j1)
                 )
-    for flag, j in ((Sd, 1), (N, npy)):
+    for flag, j, edge in ((Sd, 1, "s"), (N, npy, "n")):
         if flag:
             vrow = row(vc, j)
+            _count_sign("fxadv_vt_" + edge, vrow * dt > 0.0)
             vt[isd + o : ied + o + 1, j + o : j + o + 1] = np.where(vrow * dt > 0.0, vrow / row(m.sin_sg4, j - 1), vrow / row(m.sin_sg2, j))
             i0, i1 = max(3, is_), min(npx - 2, ie + 1)
             if not W:
@@ -228,18 +280,20 @@ def divergence_damping(D: Dom, u, v, va, ptc, vort, ua, divg_d, vc, uc, delpc, k
         R = S(is_ - 1, ie + 1, js, je + 1)
         Rm = S(is_ - 1, ie + 1, js - 1, je)
         ptc[R] = (u[R] - 0.5 * (va[Rm] + va[R]) * m.cosa_v[R]) * m.dyc[R] * m.sina_v[R]
-        for flag, j in ((Sd, 1), (N, npy)):
+        for flag, j, edge in ((Sd, 1, "s"), (N, npy, "n")):
             if flag:
                 R1 = S(is_ - 1, ie + 1, j, j)
                 R1m = S(is_ - 1, ie + 1, j - 1, j - 1)
+                _count_sign("div0_ptc_" + edge, vc[R1] * dt > 0.0)
                 ptc[R1] = np.where(vc[R1] * dt > 0.0, u[R1] * m.dyc[R1] * m.sin_sg4[R1m], u[R1] * m.dyc[R1] * m.sin_sg2[R1])
         R = S(is_, ie + 1, js - 1, je + 1)
         Rm = S(is_ - 1, ie, js - 1, je + 1)
         vort[R] = (v[R] - 0.5 * (ua[Rm] + ua[R]) * m.cosa_u[R]) * m.dxc[R] * m.sina_u[R]
-        for flag, i in ((W, 1), (E, npx)):
+        for flag, i, edge in ((W, 1, "w"), (E, npx, "e")):
             if flag:
                 R1 = S(i, i, js - 1, je + 1)
                 R1m = S(i - 1, i - 1, js - 1, je + 1)
+                _count_sign("div0_vort_" + edge, uc[R1] * dt > 0.0)
                 vort[R1] = np.where(uc[R1] * dt > 0.0, v[R1] * m.dxc[R1] * m.sin_sg3[R1m], v[R1] * m.dxc[R1] * m.sin_sg1[R1])
         delpc[Rc] = vort[S(is_, ie + 1, js - 1, je)] - vort[Rc] + ptc[S(is_ - 1, ie, js, je + 1)] - ptc[Rc]
         if D.sw:
@@ -251,6 +305,7 @@ def divergence_damping(D: Dom, u, v, va, ptc, vort, ua, divg_d, vc, uc, delpc, k
         if D.nw:
             delpc[1 + o, npy + o] += vort[1 + o, npy + o]
         delpc[Rc] = m.rarea_c[Rc] * delpc[Rc]
+        _count_damp("0", d2_bg, dddmp * np.abs(delpc[Rc] * dt))
         damp = da_min_c * np.maximum(d2_bg, np.minimum(0.20, dddmp * np.abs(delpc[Rc] * dt)))
         vort[Rc] = damp * delpc[Rc]
         ke[Rc] += vort[Rc]
@@ -288,6 +343,7 @@ def divergence_damping(D: Dom, u, v, va, ptc, vort, ua, divg_d, vc, uc, delpc, k
         wkb = a2b_ord4(D, wk, replace=False)
         vort[Rc] = np.abs(dt) * np.sqrt(delpc[Rc] ** 2 + wkb[Rc] ** 2)
     dd8 = (da_min_c * d4_bg) ** (nord + 1)
+    _count_damp("n", d2_bg, dddmp * vort[Rc])
     damp2 = da_min_c * np.maximum(d2_bg, np.minimum(0.20, dddmp * vort[Rc]))
     vort[Rc] = damp2 * delpc[Rc] + dd8 * divg_d[Rc]
     ke[Rc] += vort[Rc]
@@ -326,6 +382,9 @@ def d_sw_levels(D: Dom, cfg, p: DSWParams, delpc, delp, pt, u, v, w, uc, vc, ua,
     Rcy = S(is_, ie, js + 1, je + 1)
     ut = np.zeros_like(delp)
     vt = np.zeros_like(delp)
+    if _COUNTS is not None:
+        for name, value in (("d_con", p.d_con), ("damp_w", p.damp_w), ("damp_vt", p.damp_vt)):
+            _COUNTS[name + ("_on" if value > 1.0e-5 else "_off")] += 1
 
     ra_x, ra_y = fxadv(D, uc, vc, crx, cry, xfx, yfx, ut, vt, dt)
 

@@ -20,7 +20,7 @@ C3 = 5.0 / 14.0
 # counting never changes a value.
 _COUNTS = None
 COUNTERS = ("ppm8_dm_clamped", "ppm8_edge_clamped", "ppm8_bl_clamped", "ppm8_br_clamped", "pert_ppm_lo", "pert_ppm_hi", "pert_ppm_flat",
-            "smt5_true_hord5", "smt5_false_hord5", "smt5_true_hord6", "smt5_false_hord6")
+            "smt5_true_hord5", "smt5_false_hord5", "smt5_true_hord6", "smt5_false_hord6", "cfl_pos", "cfl_nonpos", "cfl_gt_half")
 
 
 def enable_counters(on: bool = True) -> None:
@@ -36,13 +36,21 @@ def reset_counters() -> None:
 def counters():
     """Counts since the last reset: hord 8 -- the monotonized slope dm limited by the local range, the tile-edge value clamped
     to the range of its four cells, bl / br limited to 2 |dm|, pert_ppm's a6da < -da2 / a6da > da2 / flattening (bl br >= 0);
-    hord 5 / 6 -- the smt5 switch true / false."""
+    hord 5 / 6 -- the smt5 switch true / false; every flux -- the Courant number at its face positive (the upwind cell is the one
+    before the face) / not positive / larger than 0.5 in magnitude."""
     return dict(_COUNTS or dict.fromkeys(COUNTERS, 0))
 
 
 def _count(name, mask):
     if _COUNTS is not None:
         _COUNTS[name] += int(np.count_nonzero(mask))
+
+
+def _count_cfl(cfl):
+    if _COUNTS is not None:
+        _count("cfl_pos", cfl > 0.0)
+        _count("cfl_nonpos", ~(cfl > 0.0))
+        _count("cfl_gt_half", np.abs(cfl) > 0.5)
 
 
 def _col(D, a, i, j0, j1):
@@ -110,6 +118,7 @@ def _flux_from_blbr(D, q, c, bl, br, j0, j1, mord, cfl_scale=None):
         cfl = cc
     else:
         cfl = np.where(cc > 0.0, cc * cfl_scale[Rm], cc * cfl_scale[R0])
+    _count_cfl(cfl)
     fx1 = np.where(cc > 0.0, (1.0 - cfl) * (br[Rm] - cfl * b0[Rm]), (1.0 + cfl) * (bl[R0] + cfl * b0[R0]))
     flux = np.where(cc > 0.0, q[Rm], q[R0])
     flux = np.where(smt5[Rm] | smt5[R0], flux + fx1, flux)
@@ -215,6 +224,7 @@ def xppm8(D: Dom, q, c, j0, j1):
         bl[npx - 2 + o : npx + 1 + o, j0 + o : j1 + o + 1], br[npx - 2 + o : npx + 1 + o, j0 + o : j1 + o + 1] = nbl, nbr
     R0, Rm = S(is_, ie + 1, j0, j1), S(is_ - 1, ie, j0, j1)
     cc = c[R0]
+    _count_cfl(cc)
     flux = np.where(cc > 0.0, q[Rm] + (1.0 - cc) * (br[Rm] - cc * (bl[Rm] + br[Rm])), q[R0] + (1.0 + cc) * (bl[R0] + cc * (bl[R0] + br[R0])))
     out = np.zeros_like(q)
     out[R0] = flux
