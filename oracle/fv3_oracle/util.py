@@ -225,7 +225,7 @@ def fill_corners_dgrid_vector(D: Dom, x, y, sign=-1.0):
 
 # ---------------------------------------------------------------------------------------------
 # Named alternatives for the restatements DESIGN.md §2 lists as uncertain.  One environment variable, read by the oracle
-# (here) AND by the library (fv3_alt in csrc/fv3_common.h): FV3_ALT="name[,name...]".  Default (unset) = the choice both were
+# (here) AND by the library (fv3_alt in csrc/fv3_switch.h): FV3_ALT="name[,name...]".  Default (unset) = the choice both were
 # written with.  The point: the first run against real reference savepoints (tools/gen_golden.py + tests/test_reference_golden*.py)
 # can try the alternatives in one pass -- `FV3_ALT=dz_damp_scaled pytest tests/test_reference_golden_dynamics.py` -- instead of one
 # debugging session per suspect.  Known names:

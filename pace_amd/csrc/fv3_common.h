@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/fv3_mi355x.h"
+#include "fv3_switch.h"
 
 #ifdef FV3_HOST_EMU
 #define FV3_HD
@@ -341,16 +342,6 @@ extern std::string g_fv3_create_error;
 int fv3_fail(fv3_ctx *c, int code, const std::string &msg);
 int fv3_halo_step(fv3_ctx *c, int update, int phase, void *stream);  // fv3_halo.hip
 void *fv3_dev_alloc(fv3_ctx *c, size_t bytes);
-// FV3_ALT="name[,name...]": the named alternatives of the restatements DESIGN §2 lists as uncertain -- the same variable and names the
-// oracle reads (oracle/fv3_oracle/util.py: alt), so that one run against reference savepoints can try them.  Read per call.
-inline bool fv3_alt(const char *name) {
-  const char *e = getenv("FV3_ALT");
-  if (!e) return false;
-  const size_t n = strlen(name);
-  for (const char *p = e; (p = strstr(p, name)) != nullptr; p += n)
-    if ((p == e || p[-1] == ',' || p[-1] == ' ') && (p[n] == 0 || p[n] == ',' || p[n] == ' ')) return true;
-  return false;
-}
 bool fv3_pp_ensure(fv3_ctx *c);  // (fv3_ctx.hip) the ping-pong buffers of fv3_acoustic_step, allocated on first use
 bool fv3_acc_slots_ensure(fv3_ctx *c, int n_sub_steps);  // (fv3_ctx.hip) the per-sub-step flux arrays of the deferred accumulation
 void fv3_h2d(void *dst, const void *src, size_t bytes);
@@ -442,7 +433,7 @@ __global__ void __launch_bounds__(256) fv3_k2(Box b, GridMap m, F f) {
 inline GridMap fv3_grid(int gx, int gy, int nplanes, dim3 *grid) {
   const int tpp = gx * gy;
   int sshift = 0;
-  static const bool no_split = getenv("FV3_GRID_SPLIT") && getenv("FV3_GRID_SPLIT")[0] == '0';  // A/B switch
+  static const bool no_split = !fv3_sw(FV3SW_GRID_SPLIT);  // A/B switch
   if (!no_split && nplanes < 64 && (nplanes & 7) != 0) {
     while (((nplanes << sshift) & 7) != 0) ++sshift;  // 8 / gcd(nplanes, 8) sub-planes per plane
     while (sshift > 0 && (1 << sshift) > tpp) --sshift;  // (never more sub-planes than tiles)
@@ -574,7 +565,7 @@ __global__ void __launch_bounds__(256) fv3_kfr(FrameMap fm, int nkc, GridMap m, 
 }
 // FV3_FRAME_LAUNCH=split: one launch per window (A/B; read once)
 inline bool fv3_frame_split() {
-  static const bool v = getenv("FV3_FRAME_LAUNCH") && !strcmp(getenv("FV3_FRAME_LAUNCH"), "split");
+  static const bool v = fv3_sw_is(FV3SW_FRAME_LAUNCH, "split");
   return v;
 }
 #endif
@@ -1082,8 +1073,8 @@ FV3_HD inline void fv3_st_cpl(Real *p, const Real (&src)[CPL], const bool (&own)
 // of the 4- and 8-GPU runs, where the tail of the launch matters more).  16 / 32-row segments were 1-7 %
 // slower than 64 at every size measured on MI355X, 128 equal to 64.
 inline int fv3_pick_seg(long waves_at_64, int wpe) {
-  const char *e = getenv("FV3_SEG");  // (read per launch: the production-shape parity tests force 96 on small level counts)
-  if (e && atoi(e) > 0) return atoi(e);
+  const int rows = fv3_sw(FV3SW_SEG);  // (read per launch: the production-shape parity tests force 96 on small level counts)
+  if (rows > 0) return rows;
   const long slots = 256L * 4 * wpe;
   return waves_at_64 * 2 / 3 >= 8 * slots ? 96 : 64;
 }

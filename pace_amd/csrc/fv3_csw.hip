@@ -695,13 +695,13 @@ extern "C" int fv3_c_sw(fv3_ctx *c, const fv3_field *delp_, const fv3_field *pt_
   // A/B switches, same results: FV3_CSW_B_GENERIC: every point by the generic per-point stage kernels; FV3_CSW_MARCH=0: the round-1
   // form (two-row stage-B kernel on the interior rectangle, the other stages as full stage kernels); FV3_CSW_MARCH=abc: stages
   // A - C of the interior as a marching kernel, D and E as stage kernels; default: the whole interior as one marching kernel
-  const bool b_split = g.nx >= 16 && g.ny >= 16 && !getenv("FV3_CSW_B_GENERIC");
-  const char *march_env = getenv("FV3_CSW_MARCH");
-  const bool march = b_split && !(march_env && !strcmp(march_env, "0"));
-  const bool fused = march && !(march_env && !strcmp(march_env, "abc"));
+  const bool b_split = g.nx >= 16 && g.ny >= 16 && !fv3_sw(FV3SW_CSW_B_GENERIC);
+  const int march_env = fv3_sw(FV3SW_CSW_MARCH);  // (0 default, 1 "0", 2 "abc")
+  const bool march = b_split && march_env != 1;
+  const bool fused = march && march_env != 2;
   // levels one thread of the stage kernels walks (the metric terms of its point are read once for them): FV3_KC for launches
   // over whole sub-domains; 2 when they only cover the boundary windows, which are too few points to fill the chip otherwise
-  static const int win_kc = getenv("FV3_CSW_WIN_KC") ? atoi(getenv("FV3_CSW_WIN_KC")) : 2;
+  static const int win_kc = fv3_sw(FV3SW_CSW_WIN_KC);
   const int KC = fused ? win_kc : FV3_KC;
   const int nkc = (nz1 + KC) / KC;
   // interior rectangle of sub-domain t: columns [i_lo, i_hi], rows [j_lo, j_hi] (the two-row kernel needs an even row count)
@@ -734,7 +734,7 @@ extern "C" int fv3_c_sw(fv3_ctx *c, const fv3_field *delp_, const fv3_field *pt_
   // window cells only; the interior march reads the five inputs and writes interior cells only.  Neither waits for the other, so the eight
   // small window launches (1.0 ms of a few dozen waves each) go to the auxiliary stream and run BESIDE the march; stage C -- whose windows
   // read the march's ut / vt across the rim -- joins them.  FV3_CSW_WIN_OVERLAP=0: in program order (A/B; same values).  Events 0 = fork, 1 = join.
-  static const bool win_overlap = !(getenv("FV3_CSW_WIN_OVERLAP") && getenv("FV3_CSW_WIN_OVERLAP")[0] == '0');
+  static const bool win_overlap = fv3_sw(FV3SW_CSW_WIN_OVERLAP);
   fv3_stream_t sw_ = (fused && b_split && win_overlap) ? fv3_aux(c, s) : s;
   if (sw_ != s) {
     fv3_signal(c, s, 0);
@@ -755,8 +755,7 @@ extern "C" int fv3_c_sw(fv3_ctx *c, const fv3_field *delp_, const fv3_field *pt_
   // the generic form then only runs on four windows along the sub-domain boundary (and skips the interior).
   if (fused) {
     // (FV3_SEQ_UAVA=every: ua / va stored in full by every sub-step, A/B; read per call)
-    const char *uae = getenv("FV3_SEQ_UAVA");
-    csw_fused_stream(c, s, u, v, delp, pt, w, ua, va, uc, vc, ut, vt, divgd, delpc, ptc, omga, ke, vort, dt2, nord > 0, c->seq_uava_thin && !(uae && !strcmp(uae, "every")));
+    csw_fused_stream(c, s, u, v, delp, pt, w, ua, va, uc, vc, ut, vt, divgd, delpc, ptc, omga, ke, vort, dt2, nord > 0, c->seq_uava_thin && !fv3_sw_is(FV3SW_SEQ_UAVA, "every"));
   } else if (march) {
     csw_abc_stream(c, s, u, v, ua, va, uc, vc, ut, vt, divgd, dt2, nord > 0);
   } else if (b_split) {
@@ -1158,7 +1157,7 @@ extern "C" int fv3_c_sw(fv3_ctx *c, const fv3_field *delp_, const fv3_field *pt_
   // the march) go to the auxiliary stream and the operator returns without waiting for them: update_dz_c, which follows, reads ut / vt / zh only, and
   // riem_solver_c -- the first reader of the windows' delpc / ptc / wc -- is where the sequencer joins (fv3_csw_join).  Same values; c_sw shrinks by 1.1 ms and
   // update_dz_c, bandwidth-bound beside the windows, grows by 0.85: four same-box pairs gave -0.7 / -0.0 / +0.6 / +0.1 ms per sub-step.  Events 6 = fork, 7 = join.
-  static const bool defer_on = getenv("FV3_CSW_DEFER") && getenv("FV3_CSW_DEFER")[0] == '1';
+  static const bool defer_on = fv3_sw(FV3SW_CSW_DEFER);
   fv3_stream_t sd_ = (fused && defer_on && c->seq_csw_defer) ? fv3_aux(c, s) : s;
   if (sd_ != s) {
     fv3_signal(c, s, 6);

@@ -40,8 +40,7 @@ void *fv3_dev_alloc(fv3_ctx *c, size_t bytes) {
 bool fv3_acc_slots_ensure(fv3_ctx *c, int n) {
   if (n < 2 || c->acc_state < 0) return false;  // (one sub-step per call: nothing to defer)
   if ((int)c->acc_slots.size() >= 2 * n) return true;
-  const char *e = getenv("FV3_ACC_DEFER");
-  if (e && e[0] == '0') {
+  if (!fv3_sw(FV3SW_ACC_DEFER)) {
     c->acc_state = -1;
     return false;
   }
@@ -68,8 +67,7 @@ bool fv3_acc_slots_ensure(fv3_ctx *c, int n) {
 bool fv3_pp_ensure(fv3_ctx *c) {
   if (c->pp_buf[0]) return true;
   if (c->pp_state < 0) return false;
-  const char *e = getenv("FV3_PINGPONG");
-  if (e && e[0] == '0') {
+  if (!fv3_sw(FV3SW_PINGPONG)) {
     c->pp_state = -1;
     return false;
   }
@@ -432,9 +430,7 @@ int fv3_ctx_create(fv3_ctx **out, const fv3_gridspec *spec, const fv3_griddata *
     // 460 of 512 registers); since the chains moved into the marches (round 3) what is left are launches of a few waves per CU that
     // last as long as one wave's march: beside the marches they cost nothing (C768: d_sw 55.8 -> 54.9 ms; the 1/8 share of an
     // 8-GPU run: 8.98 -> 8.8 ms).  Bitwise the same state either way (tests/test_gpu_invariants.py).
-    const char *e = getenv("FV3_AUX_STREAM");
-    const char *m = getenv("FV3_TP2D_MODE");  // the staged A/B form recomputes the damping fluxes in shared scratch
-    c->aux_on = !(e && e[0] == '0') && !(m && !strcmp(m, "staged"));
+    c->aux_on = fv3_sw(FV3SW_AUX_STREAM) && !fv3_sw_is(FV3SW_TP2D_MODE, "staged");  // (the staged A/B form recomputes the damping fluxes in shared scratch)
     hipStream_t st;
     if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess) c->aux_stream = (void *)st;
     if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess) c->comm_stream = (void *)st;
@@ -675,7 +671,7 @@ int fv3_gather_run(fv3_ctx *c, const fv3_gather_plan *p, void *dst, int64_t dks,
 int fv3_gather_run_jobs(fv3_ctx *c, const fv3_gather_job *jobs, int n, void *stream) {
   if (!c || (n && !jobs) || n < 0) return FV3_ERR_ARG;
 #ifndef FV3_HOST_EMU
-  static const bool batch_off = getenv("FV3_GATHER_BATCH") && getenv("FV3_GATHER_BATCH")[0] == '0';
+  static const bool batch_off = !fv3_sw(FV3SW_GATHER_BATCH);
   if (!batch_off) {
     GatherBatch b;
     b.n = 0;

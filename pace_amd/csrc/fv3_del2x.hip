@@ -292,19 +292,17 @@ void d2_launch(fv3_ctx *c, fv3_stream_t s, const Real *q, Real *out, Real cd, co
 int fv3_del2_heat_fused(fv3_ctx *c, const fv3_field *q_, double cdd, int nmax, const fv3_field *delp_, const fv3_field *delz_, const fv3_field *cappa_,
                         const fv3_field *pt_, double delt, bool keep_q, void *stream) {
   if (!c) return FV3_ERR_ARG;
-  const char *e = getenv("FV3_DEL2_FUSED");  // (read per call: the parity test flips it in one process)
-  if (e && e[0] == '0') return 1;
+  if (!fv3_sw(FV3SW_DEL2_FUSED)) return 1;  // (read per call: the parity test flips it in one process)
   const Geo g = c->g;
   if (nmax < 3 || g.nx < 10 || g.ny < 10 || g.nh != 3) return 1;
   FV3_FIELD(q, q_) FV3_FIELD(delp, delp_) FV3_FIELD(delz, delz_) FV3_FIELD(cappa, cappa_) FV3_FIELD(pt, pt_)
   fv3_stream_t s = (fv3_stream_t)stream;
-  if (getenv("FV3_DEBUG_DEL2")) fprintf(stderr, "[del2_heat_fused] %d x %d, keep_q %d\n", g.nx, g.ny, (int)keep_q);
+  if (fv3_sw(FV3SW_DEBUG_DEL2)) fprintf(stderr, "[del2_heat_fused] %d x %d, keep_q %d\n", g.nx, g.ny, (int)keep_q);
   del2_fill_corners(c, s, q);
   // FV3_DEL2_HEAT=fused: the heating as the epilogue of the third iteration (nothing of the smoothed field stored); default: the smoothed field goes to
   // scratch and the heating is its own launch (experiment R5-24: the fused epilogue's exp / log / divisions make the tile kernel issue-bound at
   // two waves per SIMD -- 6.6 ms -- where the two launches are each bound by their bytes)
-  const char *hm = getenv("FV3_DEL2_HEAT");
-  const bool heat_in = hm && !strcmp(hm, "fused");
+  const bool heat_in = fv3_sw_is(FV3SW_DEL2_HEAT, "fused");
   Real *out = keep_q || !heat_in ? c->scratch[SC_A] : nullptr;
   const D2Heat h{delp, delz, cappa, pt, (Real)(-c->cst.rdgas / c->cst.grav), (Real)(c->cst.cp_air - c->cst.rdgas), (Real)delt, true};
   if (heat_in)

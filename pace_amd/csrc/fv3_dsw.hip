@@ -161,7 +161,7 @@ void fxadv(fv3_ctx *c, fv3_stream_t s, const Real *uc, const Real *vc, Real *crx
            Real *cy, bool thin_ut) {
   const Geo g = c->g;
   const bool first = c->seq_acc_first;  // (the sequencer's first sub-step of a call: cx / cy hold nothing yet -- 0 + cr, the field is not read)
-  static const bool full_ut = getenv("FV3_FXADV_FULL_UT") != nullptr;  // A/B switch
+  static const bool full_ut = fv3_sw(FV3SW_FXADV_FULL_UT);  // A/B switch
   if (full_ut) thin_ut = false;
   const int isd = 1 - g.nh, ied = g.nx + g.nh, jsd = 1 - g.nh, jed = g.ny + g.nh;
   // Interior kernel, two levels per thread: away from the tile-edge rows / columns the contravariant wind is one
@@ -399,7 +399,7 @@ static void ke_stream_t(fv3_ctx *c, fv3_stream_t s, const Real *u, const Real *v
   // workgroups of an XCD, so the tile's four metric rows (cosa, rsina, rdx, rdy: 4 of the 9 row reads of a step) are fetched into that XCD's L2
   // once per KB levels -- plane-major, the 4.8 MB of metric terms of a 384^2 sub-domain do not survive a 4 MB L2 from one level to the next.
   // FV3_KE_KB=0: plane-major (A/B).
-  static const int kb_env = getenv("FV3_KE_KB") ? atoi(getenv("FV3_KE_KB")) : 16;
+  static const int kb_env = fv3_sw(FV3SW_KE_KB);
   const int KB = kb_env > 0 ? (kb_env < nk ? kb_env : nk) : 0;
   const int nblk = KB ? (nk + KB - 1) / KB : 0;
   launch_waves<4>(c, s, KB ? KB : nstrip, KB ? nstrip * nseg : nseg, KB ? g.nsub * nblk : g.nsub * nk, smem, [=] FV3_HD(const Blk &blk_, char *smem_) {
@@ -664,7 +664,7 @@ static void divdamp_stream(fv3_ctx *c, fv3_stream_t s, const Real *divgd, Real *
   const int *nord_k = g.nord;
   const MPtr divg_u = g.divg_u, divg_v = g.divg_v, rarea_c = g.rarea_c;
   // level-major launch geometry (see ke_stream): the three metric rows are 3 of the 4 row reads of a step
-  static const int kb_env = getenv("FV3_KE_KB") ? atoi(getenv("FV3_KE_KB")) : 16;
+  static const int kb_env = fv3_sw(FV3SW_KE_KB);
   const int KB = kb_env > 0 ? (kb_env < nk ? kb_env : nk) : 0;
   const int nblk = KB ? (nk + KB - 1) / KB : 0;
   launch_waves<4>(c, s, KB ? KB : nstrip, KB ? nstrip * nseg : nseg, KB ? g.nsub * nblk : g.nsub * nk, smem, [=] FV3_HD(const Blk &blk_, char *smem_) {
@@ -895,8 +895,7 @@ static void divdamp_patches(fv3_ctx *c, fv3_stream_t s, const Real *divgd, Real 
 bool dsw_honors_acc_first(const fv3_ctx *c) {
   int nmax = 0;
   for (int k = 0; k < c->g.nz; ++k) nmax = std::max(nmax, std::max(c->nord_v_h[k], std::max(c->nord_w_h[k], c->nord_t_h[k])));
-  const char *sc_env = getenv("FV3_DSW_SCALARS");
-  return !(sc_env && !strcmp(sc_env, "separate")) && nmax <= 2 && c->zeros;
+  return !fv3_sw_is(FV3SW_DSW_SCALARS, "separate") && nmax <= 2 && c->zeros;
 }
 
 // Deferred accumulation of the Courant numbers (fv3_ctx::acc_slots): crx / cry of the n sub-steps of a call, each in its own array, summed ONCE into cx / cy on
@@ -994,10 +993,10 @@ int fv3_d_sw_out(fv3_ctx *c, const fv3_field *delpc_, const fv3_field *delp_, co
   Deln dn_w{g.nord_w, tab.d6_w, g.damp_w, 0, (Real)0, false, (Real)1.0e-5, nord_max_w};
   Deln dn_t{g.nord_t, tab.tp_t, g.damp_t, 0, (Real)0, false, (Real)1.0e-4, nord_max_t};
   // FV3_DSW_SCALARS=separate: the four transports as four launches + the division kernel (round-1 form, A/B reference)
-  const char *sc_env = getenv("FV3_DSW_SCALARS");  // (read per call: the A/B parity test flips it in one process)
-  const bool fused_scalars = !(sc_env && !strcmp(sc_env, "separate")) && nord_max_v <= 2 && nord_max_t <= 2 && nord_max_w <= 2;
+  const int sc_env = fv3_sw(FV3SW_DSW_SCALARS);  // (0 default, 1 separate, 2 quad; read per call: the A/B parity test flips it in one process)
+  const bool fused_scalars = sc_env != 1 && nord_max_v <= 2 && nord_max_t <= 2 && nord_max_w <= 2;
   if (c->seq_acc_first && !fused_scalars) return fv3_fail(c, FV3_ERR_ARG, "d_sw: the sequencer's first-sub-step form of the accumulators needs the fused scalar marches");
-  const int scalars_mode = sc_env && !strcmp(sc_env, "quad") ? 0 : 1;
+  const int scalars_mode = sc_env == 2 ? 0 : 1;
   // deferred accumulation of the Courant numbers (fv3_step.hip): cx / cy are not touched by fxadv; crx / cry are this sub-step's own arrays (the sequencer hands them in)
   const bool acc_defer = c->seq_acc_defer;
   if (acc_defer && !fused_scalars) return fv3_fail(c, FV3_ERR_ARG, "d_sw: the sequencer's deferred accumulation needs the fused scalar marches (fxadv with the Courant numbers)");
@@ -1011,16 +1010,15 @@ int fv3_d_sw_out(fv3_ctx *c, const fv3_field *delpc_, const fv3_field *delp_, co
     // Levels from fd_k0 on (every chain switched on and of order 2: all but the sponge layers) run the chains INSIDE the marches
     // (fv3_tp4.hip, FD); only the faces on the cube-corner patches are computed here for them.  FV3_DSW_DELN=arrays: the
     // chains of every level as del6_stream launches (round-2 form, A/B reference).
-    const char *dn_env = getenv("FV3_DSW_DELN");  // (read per call: the A/B parity test flips it in one process)
     int fd_k0 = g.nz;
-    if (!(dn_env && !strcmp(dn_env, "arrays")) && scalars_mode == 1) {
+    if (!fv3_sw_is(FV3SW_DSW_DELN, "arrays") && scalars_mode == 1) {  // (read per call: the A/B parity test flips it in one process)
       for (int k = g.nz - 1; k >= 0; --k) {
         const bool all2 = c->nord_v_h[k] == 2 && c->nord_w_h[k] == 2 && c->nord_t_h[k] == 2 && c->damp_vt_h[k] > 1.0e-4 && c->damp_w_h[k] > 1.0e-5 && c->damp_t_h[k] > 1.0e-4;
         if (!all2) break;
         fd_k0 = k;
       }
     }
-    if (getenv("FV3_DEBUG_FD")) fprintf(stderr, "[d_sw] fd_k0 = %d of %d\n", fd_k0, g.nz);
+    if (fv3_sw(FV3SW_DEBUG_FD)) fprintf(stderr, "[d_sw] fd_k0 = %d of %d\n", fd_k0, g.nz);
     fv3_signal(c, s, 0);
     fxadv(c, s, uc, vc, crx, cry, xfx, yfx, ut, vt, dt, acc_defer ? nullptr : cx, acc_defer ? nullptr : cy, true);
     fv3_signal(c, s, 5);  // (fxadv done: what the wind branch on the auxiliary stream waits for, see below)
@@ -1134,7 +1132,7 @@ int fv3_d_sw_out(fv3_ctx *c, const fv3_field *delpc_, const fv3_field *delp_, co
   Real *vdamp = c->scratch[SC_DN_D2];  // damping field "vort" on corners
   int fdw_k0 = g.nz;
   bool keep_uv_dx = false;
-  const char *he = getenv("FV3_DSW_HEAT");
+  const bool heat_separate = fv3_sw_is(FV3SW_DSW_HEAT, "separate");
   bool heat_in_march = false;  // the vorticity march forms the damping heat (set with fdw_k0 below)
   const fv3_stream_t s_main = s;
   bool sponge_forked = false;  // the sponge levels' wind chain runs on the auxiliary stream (forked at the top of wind_branch, joined after the vorticity march)
@@ -1150,29 +1148,26 @@ int fv3_d_sw_out(fv3_ctx *c, const fv3_field *delpc_, const fv3_field *delp_, co
   // itself and runs wk's del-n chain inside its march (tp2d TF_WIND | TF_FD) -- no absolute-vorticity field, no del6_stream launch
   // over those levels but for the tile-edge strips.  FV3_DSW_VORT_DELN=arrays: the round-2 form (A/B reference).
   {
-    const char *e = getenv("FV3_DSW_VORT_DELN"), *m = getenv("FV3_TP2D_MODE"), *m6 = getenv("FV3_DEL6_MODE");
-    const bool off = (e && !strcmp(e, "arrays")) || (m && !strcmp(m, "staged")) || (m6 && !strcmp(m6, "staged")) || keep_uv_dx;
+    const bool off = fv3_sw_is(FV3SW_DSW_VORT_DELN, "arrays") || fv3_sw_is(FV3SW_TP2D_MODE, "staged") || fv3_sw_is(FV3SW_DEL6_MODE, "staged") || keep_uv_dx;
     if (!off)
       for (int k = g.nz - 1; k >= 0; --k) {
         if (!(c->nord_v_h[k] == 2 && c->damp_vt_h[k] > 1.0e-5)) break;
         fdw_k0 = k;
       }
   }
-  heat_in_march = cf.d_con > 1.0e-5 && !(he && !strcmp(he, "separate")) && fdw_k0 <= nz1 && tp2d_fd_lean(c, cf.hord_vt, fdw_k0, nz1);
+  heat_in_march = cf.d_con > 1.0e-5 && !heat_separate && fdw_k0 <= nz1 && tp2d_fd_lean(c, cf.hord_vt, fdw_k0, nz1);
   // Round 5, FV3_DSW_VORT_IN_KE=1 (experiment R5-30, off by default): the corner-KE march, which reads u and v anyway, forms the vorticity of the cells under
   // its corners -- columns 4 .. nx - 2, rows 3 .. ny - 3 at least -- and this launch only serves the four windows of the frame around them (sub-domains
   // without a tile edge on a side get those cells from both: the same values).  Same bits; measured neutral: the launch goes from 1.61 to 0.25 ms, the march
   // from 3.00 to 4.15 (23 more registers at four waves per SIMD, three more metric rows, one more store stream).
-  const char *vk_env = getenv("FV3_DSW_VORT_IN_KE");  // (read per call: the parity test flips it in one process)
-  const bool vort_in_ke = vk_env && vk_env[0] == '1' && !keep_uv_dx && getenv("FV3_KE_STAGED") == nullptr && g.nx >= 12 && g.ny >= 12;
+  const bool vort_in_ke = fv3_sw(FV3SW_DSW_VORT_IN_KE) && !keep_uv_dx && !fv3_sw(FV3SW_KE_STAGED) && g.nx >= 12 && g.ny >= 12;
   // Round 6: levels from kfz on run the FUSED wind stage (fv3_wind.hip: vorticity, corner KE, damping chain, corner interpolation and the damping in one
   // march); the launches below then only serve the levels under kfz (the sponge layers: no chain, absolute-vorticity field).  FV3_DSW_WINDSTAGE=staged:
   // every level through the staged kernels (A/B; read per call: the parity test flips it).
   int kfz = g.nz;
   {
-    const char *we = getenv("FV3_DSW_WINDSTAGE");
-    static const bool ke_staged_env = getenv("FV3_KE_STAGED") != nullptr, dd_staged_env = getenv("FV3_DIVDAMP_STAGED") != nullptr;
-    const bool off = (we && !strcmp(we, "staged")) || ke_staged_env || dd_staged_env || keep_uv_dx || vort_in_ke || nord_max > DD_NMAX || nord_max <= 0 || g.nx < 8 || g.ny < 8;
+    static const bool ke_staged_env = fv3_sw(FV3SW_KE_STAGED), dd_staged_env = fv3_sw(FV3SW_DIVDAMP_STAGED);
+    const bool off = fv3_sw_is(FV3SW_DSW_WINDSTAGE, "staged") || ke_staged_env || dd_staged_env || keep_uv_dx || vort_in_ke || nord_max > DD_NMAX || nord_max <= 0 || g.nx < 8 || g.ny < 8;
     if (!off)
       for (int k = g.nz - 1; k >= fdw_k0; --k) {
         if (!(c->nord_h[k] >= 1 && c->nord_h[k] <= DD_NMAX)) break;
@@ -1187,16 +1182,15 @@ int fv3_d_sw_out(fv3_ctx *c, const fv3_field *delpc_, const fv3_field *delp_, co
   // 3 = join after the march).  FV3_DSW_SPONGE_WIND=serial: program order (A/B; per call).
   fv3_stream_t ss = s;
   {
-    const char *spe = getenv("FV3_DSW_SPONGE_WIND");
-    if (kfz <= nz1 && ks1 >= 0 && fdw_k0 <= kfz && s == s_main && !(spe && !strcmp(spe, "serial"))) ss = fv3_aux(c, s);
+    if (kfz <= nz1 && ks1 >= 0 && fdw_k0 <= kfz && s == s_main && !fv3_sw_is(FV3SW_DSW_SPONGE_WIND, "serial")) ss = fv3_aux(c, s);
     if (ss != s) {
       fv3_signal(c, s, 2);
       fv3_wait(c, ss, 2);
       sponge_forked = true;
     }
-    if (getenv("FV3_DEBUG_FD")) fprintf(stderr, "[d_sw] sponge levels' wind chain: levels 0..%d (fdw_k0 %d) %s\n", ks1, fdw_k0, ss != s ? "on the auxiliary stream" : "in program order");
+    if (fv3_sw(FV3SW_DEBUG_FD)) fprintf(stderr, "[d_sw] sponge levels' wind chain: levels 0..%d (fdw_k0 %d) %s\n", ks1, fdw_k0, ss != s ? "on the auxiliary stream" : "in program order");
   }
-  if (getenv("FV3_DEBUG_FD")) fprintf(stderr, "[d_sw] fused wind stage on levels %d..%d of %d\n", kfz, nz1, g.nz);
+  if (fv3_sw(FV3SW_DEBUG_FD)) fprintf(stderr, "[d_sw] fused wind stage on levels %d..%d of %d\n", kfz, nz1, g.nz);
   // (two levels per thread: the six metric terms are read once)
   auto vort_cells = [=] FV3_HD(int t, int kp, int i, int j) {
     const long m2 = t * g.st2;
@@ -1228,7 +1222,7 @@ int fv3_d_sw_out(fv3_ctx *c, const fv3_field *delpc_, const fv3_field *delp_, co
       launch3(c, ss, Box{isd, ied, jsd, jed, 0, nkc - 1}, vort_cells);
   }
   // ---- kinetic energy on corners (vb * ytp_v + ub * xtp_u)
-  static const bool ke_staged = getenv("FV3_KE_STAGED") != nullptr;  // A/B switch for profiling
+  static const bool ke_staged = fv3_sw(FV3SW_KE_STAGED);  // A/B switch for profiling
   // ke_value: one corner, any position (tile-edge forms of ub / vb, one-sided PPM, corner overrides)
   auto ke_value = [=] FV3_HD(int t, int k, int i, int j) -> Real {
     const int fl = g.flags[t];
@@ -1310,7 +1304,7 @@ int fv3_d_sw_out(fv3_ctx *c, const fv3_field *delpc_, const fv3_field *delp_, co
   // ---- divergence damping.  delpc: un-iterated divergence; divgd iterated in place; uc / vc are
   //      the work arrays of the iteration exactly as in the reference (their C-grid values are dead).
   // nord == 0 levels: divergence of the D-grid wind on the fly; nord > 0 levels: delpc = divgd
-  static const bool staged_dd = getenv("FV3_DIVDAMP_STAGED") != nullptr;  // A/B switch for profiling
+  static const bool staged_dd = fv3_sw(FV3SW_DIVDAMP_STAGED);  // A/B switch for profiling
   // the marching iteration writes its result beside divgd, so the un-iterated divergence stays readable there and
   // the nord > 0 levels need no copy of it into delpc
   const bool dd_sep = !(staged_dd || nord_max > DD_NMAX);
@@ -1407,14 +1401,13 @@ int fv3_d_sw_out(fv3_ctx *c, const fv3_field *delpc_, const fv3_field *delp_, co
       // The vorticity march's damping-heat epilogue wants copies of the winds on its segment / strip boundaries, made before it updates them in place: this
       // march has every row of u and v in registers, so it stores them (sx_side_copy then only serves the levels under kfz).  Not beside the scalar marches:
       // the arrays hold their new fields then.  FV3_DSW_SIDE=copy: the separate copies (A/B; read per call).
-      const char *sd = getenv("FV3_DSW_SIDE");
-      if (heat_in_march && s == s_main && !(sd && !strcmp(sd, "copy"))) {
+      if (heat_in_march && s == s_main && !fv3_sw_is(FV3SW_DSW_SIDE, "copy")) {
         ws.u_side = c->scratch[SC_N];
         ws.v_side = c->scratch[SC_O];
         ws.side_seg = sx_march_seg(c, nz1 - fdw_k0 + 1);
         side_from = kfz;
       }
-      if (getenv("FV3_DEBUG_FD")) fprintf(stderr, "[d_sw] side copies by the wind stage: %s (segment %d)\n", ws.u_side ? "yes" : "no", ws.side_seg);
+      if (fv3_sw(FV3SW_DEBUG_FD)) fprintf(stderr, "[d_sw] side copies by the wind stage: %s (segment %d)\n", ws.u_side ? "yes" : "no", ws.side_seg);
       wind_stage_march(c, s, ws);
       // (two launches: with ke_value and a2b_point in one closure the geometry block went to scratch memory -- 1600 B per lane, 7 ms for these 3 % of the corners)
       launch_frame_w(c, s, Frame{{Box{1, 3, 1, g.ny + 1, kfz, nz1}, Box{g.npx - 2, g.npx, 1, g.ny + 1, 0, 0}, Box{1, g.nx + 1, 1, 3, 0, 0}, Box{1, g.nx + 1, g.npy - 2, g.npy, 0, 0}}},
@@ -1465,7 +1458,7 @@ int fv3_d_sw_out(fv3_ctx *c, const fv3_field *delpc_, const fv3_field *delp_, co
   // Measured (same box, alternating runs, C768): d_sw 51.6 -> 50.8 ms, but the halo copies that run inside d_sw 1.96 -> 2.5 and the sub-step
   // 113.6 -> 114.0 ms: the branch takes from the marches what it gains -- one d_sw call moves 252 GB in 51 ms = 4.9 TB/s, i.e. the operator
   // as a whole is at the bandwidth the chip sustains; overlapping its parts creates no capacity.  Off by default (FV3_DSW_WIND_OVERLAP=1).
-  static const bool wind_overlap_off = !(getenv("FV3_DSW_WIND_OVERLAP") && getenv("FV3_DSW_WIND_OVERLAP")[0] == '1');
+  static const bool wind_overlap_off = !fv3_sw(FV3SW_DSW_WIND_OVERLAP);
   for (int k = 0; k < g.nz; ++k) keep_uv_dx = keep_uv_dx || (c->d_con_h[k] > 1.0e-5 && !(c->damp_vt_h[k] > 1.0e-5));
   const bool wind_overlap = fused_scalars && s2 != s && !wind_overlap_off && !keep_uv_dx;
   if (wind_overlap) {

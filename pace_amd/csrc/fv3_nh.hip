@@ -477,12 +477,12 @@ struct Sim1W {
 #endif
 // LDS line budget of the wave solver; above it (very deep columns) the callers fall back to the column kernels
 inline bool riem_wave_ok(const Geo &g, bool heavy = false) {
-  static const char *e = getenv("FV3_RIEM_MODE");
-  if (e && !strcmp(e, "columns")) return false;
+  static const int e = fv3_sw(FV3SW_RIEM_MODE);  // (0 default, 1 columns, 2 wave)
+  if (e == 1) return false;
   const size_t line = (size_t)g.nz * FV3_WAVE * sizeof(Real) * (FV3_RIEM_GL ? 2 : 1);
   // heavy = riem_solver3 (7 exp/log per level): below 4 waves per CU (line > 40 KB: 127 levels in fp64) the
   // bandwidth-bound column form is faster (25.7 vs 29.1 ms at C768 L127 fp64); riem_solver_c still gains (24.7 vs 29.2)
-  if (heavy && !(e && !strcmp(e, "wave")) && line > 40 * 1024) return false;
+  if (heavy && e != 2 && line > 40 * 1024) return false;
   if ((g.nz + 2) * g.sk * (long)sizeof(Real) >= (1L << 32)) return false;  // (KW_: 32-bit byte offsets inside a sub-domain's field)
   return line <= (FV3_RIEM_GL ? 160 : 64) * 1024 && g.nz >= 3;
 }
@@ -490,7 +490,7 @@ inline bool riem_gam_lds(const Geo &) { return FV3_RIEM_GL != 0; }
 // gam in the accumulation registers (fv3_agpr.h; 80 levels in fp64, 128 in fp32); FV3_RIEM_REGS=0: through the scratch field (A/B, same values).
 // (A first attempt let the COMPILER index a register-tuple array: riem_solver_c 9.64 -> 13.84 ms -- DESIGN §7.)
 inline bool riem_reg_arrays(const Geo &g) {
-  static const bool off = getenv("FV3_RIEM_REGS") && getenv("FV3_RIEM_REGS")[0] == '0';
+  static const bool off = !fv3_sw(FV3SW_RIEM_REGS);
   return !off && !FV3_RIEM_GL && g.nz < (int)FV3_KREG_LEVELS;  // (level k sits in slot k + 1)
 }
 
@@ -785,8 +785,7 @@ extern "C" int fv3_riem_solver3(fv3_ctx *c, int last_call, double dtd, const fv3
     Real *const zn = c->dz_scan_src;  // (update_dz_d left its scan to this call: see fv3_ctx::seq_dz_scan)
     // Round 6: inside the sequencer only the LAST sub-step of an acoustic call stores the layer thickness -- the sub-steps between work from zh, and what reads delz
     // (the heights of the next call, the diffusive heating, the remap) comes after the last one: one field write less in five of six sub-steps.  FV3_SEQ_DELZ=every: A/B.
-    const char *sde = getenv("FV3_SEQ_DELZ");
-    const bool store_delz = !(c->seq_delz_dead && !(sde && !strcmp(sde, "every")));
+    const bool store_delz = !(c->seq_delz_dead && !fv3_sw_is(FV3SW_SEQ_DELZ, "every"));
     const bool pre = zn != nullptr;
     const Real dzm = c->dz_scan_min;
     auto go_ = [&](auto last_tag, auto ra_tag, auto pre_tag) {
@@ -999,12 +998,9 @@ int fv3_nh_p_grad_scaled(fv3_ctx *c, const fv3_field *u_, const fv3_field *v_, c
   // copy-back passes are not spent; the inputs come back unchanged.
   // product form: the four corner interpolations and the wind update as one marching kernel (fv3_pgf.hip); FV3_NH_PGF=staged keeps
   // the four a2b_ord4 launches + the level-walking update below (A/B reference)
-  {
-    const char *e = getenv("FV3_NH_PGF");  // (read per call: the A/B parity test flips it in one process)
-    if (!(e && !strcmp(e, "staged"))) {
-      nh_pgf_fused(c, s, pp, pk3, gz, delp, u, v, dt, top, (Real)gz_scale, c->frame_pass);
-      return fv3_post(c, s, "nh_p_grad");
-    }
+  if (!fv3_sw_is(FV3SW_NH_PGF, "staged")) {  // (read per call: the A/B parity test flips it in one process)
+    nh_pgf_fused(c, s, pp, pk3, gz, delp, u, v, dt, top, (Real)gz_scale, c->frame_pass);
+    return fv3_post(c, s, "nh_p_grad");
   }
   Real *ppb = c->scratch[SC_B], *pk3b = c->scratch[SC_C], *gzb = c->scratch[SC_D], *wk1 = c->scratch[SC_A];
   if (c->frame_pass != 2) {  // (interior pass of the frame-first form: the corner fields are in scratch already)
@@ -1189,7 +1185,7 @@ static void edge_profile_wave(fv3_ctx *c, fv3_stream_t s, const Real *crx, const
   // integers among the kernel arguments), so every access stays a global load off one base.  Experiment R5-22 (update_dz_d -0.18 ms, but d_sw +0.5 ms in the
   // same processes: left off); re-measured in round 6 on the fused wind stage (R6-8: update_dz_d -0.11 / -0.20 ms, d_sw -0.0 / -0.4): the default now.
   // FV3_EP_ONE_LAUNCH=0: four launches (A/B; bitwise equal).
-  static const bool one = !(getenv("FV3_EP_ONE_LAUNCH") && getenv("FV3_EP_ONE_LAUNCH")[0] == '0');
+  static const bool one = fv3_sw(FV3SW_EP_ONE_LAUNCH);
   if (one) {
     const EpSet set{{0, (long)(xfx - crx), (long)(cry - crx), (long)(yfx - crx)}, {0, (long)(xfx_a - crx_a), (long)(cry_a - crx_a), (long)(yfx_a - crx_a)}, 4};
     edge_profile_wave1<NZ>(c, s, crx, crx_a, true, set);
@@ -1297,11 +1293,11 @@ static void edge_profile_wave1(fv3_ctx *c, fv3_stream_t s, const Real *q0, Real 
 // returns false when the level count has no register-resident instantiation (the caller then runs the generic form)
 static bool edge_profile_columns(fv3_ctx *c, fv3_stream_t s, const Real *crx, const Real *xfx, const Real *cry, const Real *yfx, Real *crx_a, Real *xfx_a, Real *cry_a,
                                  Real *yfx_a) {
-  static const bool generic = getenv("FV3_EDGE_PROFILE_GENERIC") != nullptr;  // A/B switches
-  static const bool regs = getenv("FV3_EDGE_PROFILE_REG") != nullptr;
+  static const bool generic = fv3_sw(FV3SW_EDGE_PROFILE_GENERIC);  // A/B switches
+  static const bool regs = fv3_sw(FV3SW_EDGE_PROFILE_REG);
   if (generic) return false;
   if (!regs && c->g.nz >= 2) {
-    static const bool lds = getenv("FV3_EDGE_PROFILE_LDS") != nullptr;
+    static const bool lds = fv3_sw(FV3SW_EDGE_PROFILE_LDS);
     if (c->g.nz == 79 && !lds) {
       edge_profile_wave<79>(c, s, crx, xfx, cry, yfx, crx_a, xfx_a, cry_a, yfx_a);
       return true;
@@ -1415,8 +1411,7 @@ extern "C" int fv3_update_dz_d(fv3_ctx *c, const fv3_field *zs_, const fv3_field
   // the cube-corner patches there.  FV3_DZ_DELN=arrays: the chain of every interface as one del6_stream launch (A/B reference).
   int fd_k0 = nz + 1;
   {
-    const char *e = getenv("FV3_DZ_DELN"), *m = getenv("FV3_TP2D_MODE"), *m6 = getenv("FV3_DEL6_MODE");
-    const bool off = (e && !strcmp(e, "arrays")) || (m && !strcmp(m, "staged")) || (m6 && !strcmp(m6, "staged"));
+    const bool off = fv3_sw_is(FV3SW_DZ_DELN, "arrays") || fv3_sw_is(FV3SW_TP2D_MODE, "staged") || fv3_sw_is(FV3SW_DEL6_MODE, "staged");
     if (!off)
       for (int k = nz; k >= 0; --k) {
         if (!(c->nord_v_h[k] == 2 && c->damp_vt_h[k] > 1.0e-5)) break;
@@ -1437,8 +1432,7 @@ extern "C" int fv3_update_dz_d(fv3_ctx *c, const fv3_field *zs_, const fv3_field
     del6_vt_flux_edge_strips(c, s, zh, d2, fx2, fy2, dn, false, fd_k0, nz);
   // Round 6: inside the sequencer (fv3_ctx::seq_dz_scan) the scan at the end of this operator becomes the pre-sweep of riem_solver3's wave form, which reads the
   // marched heights where this call leaves them (the free slot SC_F: riem_solver3's scratch fields are SC_A / C / D / E).  FV3_DZ_SCAN=separate: the kernel below (A/B).
-  const char *zse = getenv("FV3_DZ_SCAN");
-  const bool scan_deferred = c->seq_dz_scan && riem_wave_ok(g, true) && riem_reg_arrays(g) && !(zse && !strcmp(zse, "separate"));
+  const bool scan_deferred = c->seq_dz_scan && riem_wave_ok(g, true) && riem_reg_arrays(g) && !fv3_sw_is(FV3SW_DZ_SCAN, "separate");
   Real *znew = scan_deferred ? fy : fx;
   {
     TpEpi e{znew, nullptr, false, nullptr, nullptr, nullptr, nullptr, nullptr, true, fx2, fy2, g.damp_vt, nullptr, nullptr};
@@ -1449,7 +1443,7 @@ extern "C" int fv3_update_dz_d(fv3_ctx *c, const fv3_field *zs_, const fv3_field
     tp2d(c, s, zh, crx_a, cry_a, xfx_a, yfx_a, c->scratch[SC_J], c->scratch[SC_K], nullptr, nullptr, nullptr, c->cfg.hord_tm, nullptr, fd_k0, nz, &e);
     if (sa != s) fv3_wait(c, s, 3);
   }
-  if (getenv("FV3_DEBUG_FD")) fprintf(stderr, "[update_dz_d] closing scan: %s\n", scan_deferred ? "left to riem_solver3's pre-sweep" : "own kernel");
+  if (fv3_sw(FV3SW_DEBUG_FD)) fprintf(stderr, "[update_dz_d] closing scan: %s\n", scan_deferred ? "left to riem_solver3's pre-sweep" : "own kernel");
   if (scan_deferred) {
     c->dz_scan_src = znew;
     c->dz_scan_min = dz_min;

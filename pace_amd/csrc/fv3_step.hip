@@ -268,7 +268,7 @@ extern "C" int fv3_acoustic_step(fv3_ctx *c, const fv3_state *st, const fv3_work
   // nh_p_grad + ray_fast).  Same values either way; without a transport the split only costs launches, so it stays off
   // (FV3_FRAME_FIRST=1 / 0 forces it).
   bool frame_first = !halo && (c->nccl_comm != nullptr || c->xfer != nullptr);
-  if (const char *e = getenv("FV3_FRAME_FIRST")) frame_first = !halo && e[0] == '1';
+  if (const int e = fv3_sw(FV3SW_FRAME_FIRST); e >= 0) frame_first = !halo && e == 1;
   bool w_started = false;
   c->frame_pass = 0;
   struct PpGuard {  // (no early return leaves the halo translation switched on, or c_sw's deferred windows unjoined)
@@ -308,8 +308,7 @@ extern "C" int fv3_acoustic_step(fv3_ctx *c, const fv3_state *st, const fv3_work
   // block, not from the field): four 2.3 GB zero launches and four field reads less per call.  Round 6: the cells d_sw never writes (frame of every plane, padding
   // level) are zeroed on every call by zero_unwritten -- whatever the arrays held before the call, every cell ends up with what zero + accumulate leaves there.
   // FV3_ACC_STORE=0: zero + accumulate on every sub-step (A/B; same bits: 0 + x is what the accumulation computes on a zeroed field).
-  const char *acc_env = getenv("FV3_ACC_STORE");  // (read per call: the parity test flips it in one process)
-  const bool acc_store = !(acc_env && acc_env[0] == '0') && n_split > 0 && dsw_honors_acc_first(c);
+  const bool acc_store = fv3_sw(FV3SW_ACC_STORE) && n_split > 0 && dsw_honors_acc_first(c);  // (read per call: the parity test flips it in one process)
   if (!acc_store) {
     const fv3_field *acc[4] = {&st->mfxd, &st->mfyd, &st->cxd, &st->cyd};
     for (int a = 0; a < 4; ++a) RUN(FV3_OP_GLUE, fv3_zero(c, acc[a], stream));
@@ -323,12 +322,11 @@ extern "C" int fv3_acoustic_step(fv3_ctx *c, const fv3_state *st, const fv3_work
   // Round 6: cx / cy are formed once, at the end of the last d_sw of the call, from the sub-steps' own Courant-number arrays (fv3_dsw.hip: acc_sum; fv3_ctx::acc_slots).
   // FV3_ACC_DEFER=0 (or FV3_ACC_STORE=0, or a failed allocation of the 2 x n_split arrays): read-modify-write in every sub-step (A/B; same bits).
   const bool acc_defer = acc_store && n_split >= 2 && n_split <= FV3_ACC_MAXSTEPS && dsw_can_defer_acc(c) && fv3_acc_slots_ensure(c, n_split);
-  if (getenv("FV3_DEBUG_FD")) fprintf(stderr, "[acoustic_step] accumulators: %s\n", acc_defer ? "cx / cy formed once per call from the sub-steps' Courant numbers, mfx / mfy read-modify-write" : acc_store ? "read-modify-write, first sub-step stores" : "zeroed, read-modify-write");
+  if (fv3_sw(FV3SW_DEBUG_FD)) fprintf(stderr, "[acoustic_step] accumulators: %s\n", acc_defer ? "cx / cy formed once per call from the sub-steps' Courant numbers, mfx / mfy read-modify-write" : acc_store ? "read-modify-write, first sub-step stores" : "zeroed, read-modify-write");
   if (acc_store)
     RUN(FV3_OP_GLUE, zero_unwritten(c, &st->mfxd, &st->mfyd, &st->cxd, &st->cyd, heat_store ? &ws->heat_source : nullptr, stream));
   RUN(FV3_OP_GLUE, fv3_zero(c, &st->diss_estd, stream));
-  const char *gz_env = getenv("FV3_GZ_FIRST");  // (read per call: the parity test flips it in one process)
-  const bool gz_direct = !(gz_env && !strcmp(gz_env, "copy"));
+  const bool gz_direct = !fv3_sw_is(FV3SW_GZ_FIRST, "copy");  // (read per call: the parity test flips it in one process)
   for (int it = 0; it < n_split; ++it) {
     const int remap_step = it == n_split - 1;
     if (!w_started) HALO(FV3_HALO_W, 0);
@@ -413,7 +411,7 @@ extern "C" int fv3_acoustic_step(fv3_ctx *c, const fv3_state *st, const fv3_work
         c->prof_parent = -1;
         return st_;
       };
-      c->seq_divgd_dead = getenv("FV3_SEQ_KEEP_DIVGD") == nullptr;
+      c->seq_divgd_dead = !fv3_sw(FV3SW_SEQ_KEEP_DIVGD);
       c->seq_acc_first = acc_store && it == 0;
       c->seq_heat_first = heat_store && it == 0;
       RUN(FV3_OP_D_SW, fv3_d_sw_out(c, &ws->dsw_delpc, &f_delp[cur], &f_pt[cur], &st->u, &st->v, &f_w[cur], &st->uc, &st->vc, &st->ua, &st->va, &ws->divgd, &st->mfxd,

@@ -388,8 +388,7 @@ void del6_vt_flux_patches(fv3_ctx *c, fv3_stream_t s, const Real *q, Real *d2, R
 void del6_vt_flux(fv3_ctx *c, fv3_stream_t s, const Real *q, Real *d2, Real *fx2, Real *fy2, const Deln &dn, bool q_raw, int k0, int k1) {
   if (k0 > k1) return;
   // FV3_DEL6_MODE = staged | stream (default): the staged form is the reference / A-B path
-  static const char *mode_env = getenv("FV3_DEL6_MODE");
-  static const bool staged = mode_env && !strcmp(mode_env, "staged");
+  static const bool staged = fv3_sw_is(FV3SW_DEL6_MODE, "staged");
   if (staged || dn.nord_max > D6_NMAX)
     del6_vt_flux_staged(c, s, q, d2, fx2, fy2, dn, q_raw, k0, k1, nullptr);
   else
@@ -570,7 +569,7 @@ static void tp2d_stream_t(fv3_ctx *c, fv3_stream_t s, const Real *q, const Real 
   // Launch geometry as in fv3_tp4.hip: level-major (KB levels of one (strip, segment) tile are consecutive workgroups of an XCD, so the
   // tile's 2-D metric rows are fetched into that XCD's L2 once per KB levels instead of once per level) when KB > 0; FV3_Q4_KB=0
   // selects the plane-major form (A/B; same values, same time, 15 - 20 % more L2 misses).
-  static const int kb_env = getenv("FV3_Q4_KB") ? atoi(getenv("FV3_Q4_KB")) : FV3_Q4_KB_DEFAULT;
+  static const int kb_env = fv3_sw(FV3SW_Q4_KB);
   const int KB = kb_env > 0 ? (kb_env < nk ? kb_env : nk) : 0;
   const int nblk = KB ? (nk + KB - 1) / KB : 0;
 #if defined(FV3_STAMPS) && !defined(FV3_HOST_EMU)
@@ -1182,10 +1181,9 @@ bool tp2d_fd_lean(const fv3_ctx *c, int hord, int k0, int k1) {
   // (the contract of the FD forms -- chain of order 2 switched on at every level of the call -- checked on the host tables)
   for (int k = k0; k <= k1; ++k)
     if (k >= (int)c->nord_v_h.size() || !(c->nord_v_h[k] == 2 && c->damp_vt_h[k] > 1.0e-5)) return false;
-  static const bool hc_off = getenv("FV3_HORD_CONST") && getenv("FV3_HORD_CONST")[0] == '0';
-  static const bool fa_off = getenv("FV3_TP2D_FA") && getenv("FV3_TP2D_FA")[0] == '0';
-  const char *me = getenv("FV3_TP2D_MARCH");  // (read per call: the parity test flips it)
-  return hord == 6 && !hc_off && !fa_off && !TS_LDS_ONLY && !(me && !strcmp(me, "old"));
+  static const bool hc_off = fv3_sw(FV3SW_HORD_CONST) == 0;
+  static const bool fa_off = !fv3_sw(FV3SW_TP2D_FA);
+  return hord == 6 && !hc_off && !fa_off && !TS_LDS_ONLY && !fv3_sw_is(FV3SW_TP2D_MARCH, "old");  // (read per call: the parity test flips it)
 }
 
 static void tp2d_stream(fv3_ctx *c, fv3_stream_t s, const Real *q, const Real *crx, const Real *cry, const Real *xfx, const Real *yfx, Real *fx, Real *fy,
@@ -1207,9 +1205,9 @@ static void tp2d_stream(fv3_ctx *c, fv3_stream_t s, const Real *q, const Real *c
     tp2d_stream_t<(F)>(c, s, q, crx, cry, xfx, yfx, fx, fy, mfx, mfy, mass, hord, dn, k0, k1, epi); \
     return;
   // the two big launches of the acoustic sub-step with the PPM order as a constant (reference default 6; FV3_HORD_CONST=0: A/B)
-  static const bool hc_off = getenv("FV3_HORD_CONST") && getenv("FV3_HORD_CONST")[0] == '0';
+  static const bool hc_off = fv3_sw(FV3SW_HORD_CONST) == 0;
   // (FA: what the two callers of the FD forms guarantee -- fv3_update_dz_d / fv3_d_sw_out pass only levels whose chain is on)
-  static const bool fa_off_env = getenv("FV3_TP2D_FA") && getenv("FV3_TP2D_FA")[0] == '0';
+  static const bool fa_off_env = !fv3_sw(FV3SW_TP2D_FA);
   if (hord == 6 && !hc_off && !TS_LDS_ONLY) {
     // Round 5: the FA forms run the march of fv3_tp2x.hip (every tile: it evaluates the W / E one-sided formulas in its lanes and the cube-corner
     // remaps / patch fluxes in its general steps).  FV3_TP2D_MARCH=old: the round-4 kernel (A/B; read per call).
@@ -1260,8 +1258,7 @@ static void tp2d_stream(fv3_ctx *c, fv3_stream_t s, const Real *q, const Real *c
 void tp2d(fv3_ctx *c, fv3_stream_t s, const Real *q, const Real *crx, const Real *cry, const Real *xfx, const Real *yfx, Real *fx, Real *fy,
           const Real *mfx, const Real *mfy, const Real *mass, int hord, const Deln *dn, int k0, int k1, const TpEpi *epi) {
   // FV3_TP2D_MODE = staged | stream (default): the staged form is the reference / A-B path
-  static const char *mode_env = getenv("FV3_TP2D_MODE");
-  static const bool staged = mode_env && !strcmp(mode_env, "staged");
+  static const bool staged = fv3_sw_is(FV3SW_TP2D_MODE, "staged");
   if (k0 > k1) return;
   if (!staged) {
     tp2d_stream(c, s, q, crx, cry, xfx, yfx, fx, fy, mfx, mfy, mass, hord, dn, k0, k1, epi);

@@ -60,7 +60,7 @@ void single_march_t(fv3_ctx *c, fv3_stream_t s, const SxArgs &a, int k_lo, int k
   const int nstrip = (nx + 1 + SX_OUT - 1) / SX_OUT;
   const int seg = fv3_pick_seg((long)nstrip * ((ny + 63) / 64) * g.nsub * nk, 2);
   const int nseg = (ny + seg - 1) / seg;
-  static const int kb_env = getenv("FV3_Q4_KB") ? atoi(getenv("FV3_Q4_KB")) : FV3_Q4_KB_DEFAULT;
+  static const int kb_env = fv3_sw(FV3SW_Q4_KB);
   const int KB = kb_env > 0 ? (kb_env < nk ? kb_env : nk) : 0;
   const int nblk = KB ? (nk + KB - 1) / KB : 0;
   const long st = g.st, sk = g.sk, st2 = g.st2;

@@ -58,9 +58,6 @@
 enum { Q4_QUAD = 0, Q4_AIR = 1, Q4_TRC = 2 };
 enum { Q4_ALL = 0, Q4_INTERIOR = 1, Q4_EDGE = 2 };
 #define Q4_EW 3  // cells next to a W / E tile edge the EDGE launch owns
-#ifndef Q4_KB
-#define Q4_KB FV3_Q4_KB_DEFAULT   // > 0: that many levels of one tile are consecutive workgroups of an XCD (interior marches); 0: plane-major
-#endif
 
 // tracer identity of slot n: 0 = delp, 1 = w, 2 = q_con, 3 = pt
 template <int ROLE>
@@ -141,13 +138,13 @@ static void dsw_scalars_t(fv3_ctx *c, fv3_stream_t s, const DswScalars &a_, int 
   const Real *damp_w_k = g.damp_w, *ke_bg_k = g.ke_bg;
   const int bitLlo = TR ? FV3_S : FV3_W, bitLhi = TR ? FV3_N : FV3_E, bitMlo = TR ? FV3_W : FV3_S, bitMhi = TR ? FV3_E : FV3_N;
   // Launch geometry.  Plane-major (default before round 3): an XCD walks the tiles of one (sub-domain, level) plane, consecutive
-  // levels land on different XCDs.  Level-major (Q4_KB levels of ONE tile are consecutive workgroups of an XCD): the tile's 2-D metric
-  // rows (area, rarea, the del-n coefficients) are fetched into that XCD's L2 once per Q4_KB levels instead of once per level.
+  // levels land on different XCDs.  Level-major (FV3_Q4_KB levels of ONE tile are consecutive workgroups of an XCD): the tile's 2-D metric
+  // rows (area, rarea, the del-n coefficients) are fetched into that XCD's L2 once per FV3_Q4_KB levels instead of once per level.
   // Measured at C768 (same box, alternating runs): the same time (d_sw 54.7 / 55.05 ms level-major (16) against 55.6 / 55.06 plane-major)
   // and 14 % fewer L2 misses of the march (FETCH_SIZE 31.7 -> 24.9 GB for delp + w, 37.1 -> 30.8 for q_con + pt: the metric rows were
   // Infinity-Cache hits, not HBM reads, which is why the time does not move).  Level-major is the default; FV3_Q4_KB=0 selects
   // plane-major (A/B).
-  static const int kb_env = getenv("FV3_Q4_KB") ? atoi(getenv("FV3_Q4_KB")) : Q4_KB;
+  static const int kb_env = fv3_sw(FV3SW_Q4_KB);
   const int KB = (PART == Q4_INTERIOR && kb_env > 0) ? (kb_env < nk ? kb_env : nk) : 0;
   const int nblk = KB ? (nk + KB - 1) / KB : 0;
 #if defined(FV3_STAMPS) && !defined(FV3_HOST_EMU)
@@ -928,7 +925,7 @@ void dsw_scalars_stream(fv3_ctx *c, fv3_stream_t s, const DswScalars &a, int mod
     // auxiliary stream and run BESIDE the marches of the other levels (disjoint levels of the same arrays; the q_con + pt march of
     // a level follows the delp + w march of that level on either stream).  Events: 2 = fork, 3 = join.
     // (FV3_DSW_SPONGE_SERIAL=1: the sponge-level launches in program order on the caller's stream -- experiment R5-17)
-    static const bool sponge_serial = getenv("FV3_DSW_SPONGE_SERIAL") && getenv("FV3_DSW_SPONGE_SERIAL")[0] == '1';
+    static const bool sponge_serial = fv3_sw(FV3SW_DSW_SPONGE_SERIAL);
     fv3_stream_t s2 = kf > 0 && kf <= nz1 && !sponge_serial ? fv3_aux(c, s) : s;
     if (s2 != s) {
       fv3_signal(c, s, 2);
@@ -943,7 +940,7 @@ void dsw_scalars_stream(fv3_ctx *c, fv3_stream_t s, const DswScalars &a, int mod
     //  FV3_HORD_CONST=0 keeps the run-time form -- A/B, same values)
     //  Measured: -0.15 ms of d_sw for 12 spilled VGPRs in the two-tracer marches (the branch-free limiter needs ~24 more registers):
     //  off by default here (FV3_HORD_CONST=1 selects it), on in the single-tracer marches of fv3_tp2d.hip.
-    static const bool hc_on = getenv("FV3_HORD_CONST") && getenv("FV3_HORD_CONST")[0] == '1';
+    static const bool hc_on = fv3_sw(FV3SW_HORD_CONST) == 1;
     if (hc_on && a.hord_dp == 6 && a.hord_vt == 6 && a.hord_tm == 6) {
       dsw_scalars_t<Q4_AIR, Q4_INTERIOR, false, true, 6>(c, s, a, kf, nz1);
       if (edges) dsw_scalars_t<Q4_AIR, Q4_EDGE, false, true>(c, s, a, kf, nz1);
@@ -952,14 +949,14 @@ void dsw_scalars_stream(fv3_ctx *c, fv3_stream_t s, const DswScalars &a, int mod
     } else {
       // Round 5: EVERY tile runs the march of fv3_tp4x.hip (PPM order 6 only; W / E one-sided formulas in the lanes, cube-corner remaps and patch
       // fluxes in its general steps).  FV3_DSW_MARCH=old: the round-4 kernels on every tile (A/B; read per call: the parity test flips it).
-      const char *me = getenv("FV3_DSW_MARCH");
-      const bool px_on = !(me && !strcmp(me, "old")) && a.hord_dp == 6 && a.hord_vt == 6 && a.hord_tm == 6;
+      const int me = fv3_sw(FV3SW_DSW_MARCH);  // (0 default, 1 old, 2 coupled)
+      const bool px_on = me != 1 && a.hord_dp == 6 && a.hord_vt == 6 && a.hord_tm == 6;
       // (measured and dropped: the transposed tile-edge marches on the auxiliary stream beside the interior ones -- d_sw 51.5 ms either way)
       if (px_on) {  // (every tile: the W / E one-sided formulas in the lanes, the cube-corner remaps / patch fluxes in the general steps)
         // Round 6, FV3_DSW_MARCH=coupled (measured, NOT the default): the two roles as coupled wave pairs -- one workgroup of two waves per tile, the air-mass
         // fluxes / old air mass / shared rows handed over through LDS (fv3_tp4x.hip, PX_BOTH).  Bitwise equal and 27 GB lighter, but 24.7 ms against 14.8 for the
         // two launches at C768: a role's waves in flight are halved and every row step costs the slower role's time (EXPERIMENTS R6-5).
-        if (me && !strcmp(me, "coupled")) {
+        if (me == 2) {
           dsw_pair_march(c, s, a, 3, kf, nz1);
         } else {
           dsw_pair_march(c, s, a, 1, kf, nz1);

@@ -56,7 +56,7 @@ void pair_march_t(fv3_ctx *c, fv3_stream_t s, const DswScalars &a, int k_lo, int
   const int nstrip = (nL + 1 + PX_OUT - 1) / PX_OUT;
   const int seg = fv3_pick_seg((long)nstrip * ((nM + 63) / 64) * g.nsub * nk, PX_WPE);
   const int nseg = (nM + seg - 1) / seg;
-  static const int kb_env = getenv("FV3_Q4_KB") ? atoi(getenv("FV3_Q4_KB")) : FV3_Q4_KB_DEFAULT;
+  static const int kb_env = fv3_sw(FV3SW_Q4_KB);
   const int KB = kb_env > 0 ? (kb_env < nk ? kb_env : nk) : 0;
   const int nblk = KB ? (nk + KB - 1) / KB : 0;
   const long st = g.st, sk = g.sk, st2 = g.st2;
@@ -711,7 +711,7 @@ void pair_march_t(fv3_ctx *c, fv3_stream_t s, const DswScalars &a, int k_lo, int
 // role 1 = delp + w, 2 = q_con + pt, 3 = both as coupled wave pairs (device only; the host emulation runs the two roles one after the other: a hand-over
 // between concurrently running waves has no emulation)
 void dsw_pair_march(fv3_ctx *c, fv3_stream_t s, const DswScalars &a, int role, int k_lo, int k_hi) {
-  if (getenv("FV3_DEBUG_FD")) fprintf(stderr, "[d_sw] pair march, role %d, levels %d..%d\n", role, k_lo, k_hi);
+  if (fv3_sw(FV3SW_DEBUG_FD)) fprintf(stderr, "[d_sw] pair march, role %d, levels %d..%d\n", role, k_lo, k_hi);
   if (role == PX_AIR)
     pair_march_t<PX_AIR>(c, s, a, k_lo, k_hi);
   else if (role == PX_TRC)

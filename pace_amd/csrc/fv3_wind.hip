@@ -62,7 +62,7 @@ void wind_stage_march_t(fv3_ctx *c, fv3_stream_t s, const WindStage &a) {
   const bool store_dn = a.store_dn;
   Real *const fus = a.u_side, *const fvs = a.v_side;
   const int side_seg = (a.u_side && a.v_side) ? a.side_seg : 0;
-  static const int kb_env = getenv("FV3_KE_KB") ? atoi(getenv("FV3_KE_KB")) : 16;
+  static const int kb_env = fv3_sw(FV3SW_KE_KB);
   const int KB = kb_env > 0 ? (kb_env < nk ? kb_env : nk) : 0;
   const int nblk = KB ? (nk + KB - 1) / KB : 0;
   launch_waves<WS_WPE>(c, s, KB ? KB : nstrip, KB ? nstrip * nseg : nseg, KB ? g.nsub * nblk : g.nsub * nk, 0, [=] FV3_HD(const Blk &blk_, char *) {
@@ -415,7 +415,7 @@ void wind_stage_march_t(fv3_ctx *c, fv3_stream_t s, const WindStage &a) {
 }  // namespace
 
 void wind_stage_march(fv3_ctx *c, fv3_stream_t s, const WindStage &a) {
-  static const bool hc_off = getenv("FV3_HORD_CONST") && getenv("FV3_HORD_CONST")[0] == '0';
+  static const bool hc_off = fv3_sw(FV3SW_HORD_CONST) == 0;
   if (a.hord == 6 && !hc_off)
     wind_stage_march_t<6>(c, s, a);
   else

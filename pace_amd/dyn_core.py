@@ -43,6 +43,11 @@ _DIMS = {
 STATE_NAMES = "u v w ua va uc vc delp delz pt pe pk peln pkz q_con omga cappa mfxd mfyd cxd cyd diss_estd".split()
 
 
+def _alt(name: str) -> bool:
+    """Is ``name`` among the comma-separated alternatives of FV3_ALT?  (read per call, as the library's fv3_alt and fv3_oracle/util.py: alt do)"""
+    return name in [x.strip() for x in os.environ.get("FV3_ALT", "").split(",")]
+
+
 class DycoreState:
     """The fields of ``pyFV3.DycoreState`` the acoustic path touches
     [REF tests/main/fv3core/test_init_from_geos.py:128-199; driver/pace/driver/state.py:131-139]."""
@@ -266,7 +271,7 @@ class AcousticDynamics:
         if update_temporaries:
             for q in (state.mfxd, state.mfyd, state.cxd, state.cyd):  # every call ("empty the flux capacitors")
                 sf.call("zero", q.fref)
-            if n_map == 1 or "heat_zero_first_call" not in [x.strip() for x in os.environ.get("FV3_ALT", "").split(",")]:  # (FV3_ALT: DESIGN §2, restatement 5)
+            if n_map == 1 or not _alt("heat_zero_first_call"):  # (FV3_ALT: DESIGN §2, restatement 5)
                 sf.call("zero", self._heat_source.fref)
             sf.call("zero", state.diss_estd.fref)
         for it in range(n_split):
@@ -331,5 +336,5 @@ class AcousticDynamics:
             up["heat_source"].update()
             cd = self.c.CNST_0P20 * self._da_min
             self._hyperdiffusion(self._heat_source, cd)
-            heat_dt = timestep if "heat_dt_full" in [x.strip() for x in os.environ.get("FV3_ALT", "").split(",")] else dt  # (FV3_ALT: fv3_oracle/util.py)
+            heat_dt = timestep if _alt("heat_dt_full") else dt  # (FV3_ALT: fv3_oracle/util.py)
             self._apply_diffusive_heating(state.delp, state.delz, state.cappa, self._heat_source, state.pt, abs(heat_dt * cfg.delt_max))
