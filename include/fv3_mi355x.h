@@ -351,11 +351,33 @@ int fv3_tracer_2d_1l(fv3_ctx *, int n_tracers, const fv3_field *const *tracers, 
  * u, v, w and the tracers go from the Lagrangian layers (interfaces = pe / peln as the last acoustic sub-step left them,
  * pe's one-cell halo ring by edge_pe) to the Eulerian ones ak + bk * ps; pe, peln, pk, pkz and ps (2-D) are rebuilt.
  * Configuration of the reference configs: non-hydrostatic, T_v remapped in log(p), kord 9 everywhere, moist-cappa pkz with
- * the given cappa field, no energy fixer, no saturation adjustment, no fillz, omga untouched; nz >= 5. */
+ * the given cappa field, no energy fixer, no saturation adjustment, omga untouched; nz >= 5.  The vertical filling of negative
+ * tracer means that the reference runs at the end of the tracer part (`fill: true`) is its own entry, fv3_fillz, called right
+ * after this one with the remapped tracers and delp. */
 int fv3_remap(fv3_ctx *, int n_tracers, const fv3_field *const *tracers, const fv3_field *pt, const fv3_field *delp,
               const fv3_field *delz, const fv3_field *peln, const fv3_field *pe, const fv3_field *pk, const fv3_field *pkz,
               const fv3_field *u, const fv3_field *v, const fv3_field *w, const fv3_field *cappa, const fv3_field *ps,
               const fv3_field *wsd, void *stream);
+
+/* fillz (FV3 fv_fill.F90, default form; pyFV3 FillNegativeTracerValues: the end of the tracer part of LagrangianToEulerian with
+ * `fill: true` [REF driver/examples/configs/baroclinic_c12.yaml:56]).  In place on the compute cells 1..nx x 1..ny, levels
+ * 0 .. nz-1 of every sub-domain; halo cells and the pad level nz of the tracers are neither read nor written; dp (after the remap:
+ * the Eulerian delp) is only read.  Per column and tracer, 0-based, km = nz, in the build's Real, every product, quotient and sum
+ * rounded on its own:
+ *   top       q[0] < 0: q[1] = q[1] + (q[0] * dp[0]) / dp[1], q[0] = 0 (does not set zfix);
+ *   interior  k = 1 .. km-2 in increasing order, q[k] < 0: zfix; where q[k-1] > 0, dq = min(q[k-1] * dp[k-1], -q[k] * dp[k]) moves
+ *             from level k-1 to k (q[k-1] - dq / dp[k-1], q[k] + dq / dp[k]); where q[k] is still < 0 and q[k+1] > 0,
+ *             dq = min(q[k+1] * dp[k+1], -q[k] * dp[k]) moves from level k+1 to k; level k+1 is then visited with what is left;
+ *   bottom    k = km-1, q[k] < 0 and q[k-1] > 0: zfix; dup = min(-q[k] * dp[k], q[k-1] * dp[k-1]) moves from level k-1 to k (a
+ *             negative bottom layer under a non-positive one is left alone);
+ *   non-local where zfix: dm[k] = q[k] * dp[k] for k = 1 .. km-1, sum0 = sum dm[k], sum1 = sum max(0, dm[k]) (increasing k, from 0);
+ *             where sum0 > 0: q[k] = max(0, ((sum0 / sum1) * dm[k]) / dp[k]) for k = 1 .. km-1 (level 0 is not touched).
+ * Comparisons are plain IEEE (-0.0 and NaN take no branch; min(a, b) = a < b ? a : b; max(0, x) = x < 0 ? 0 : x in the quotient,
+ * x > 0 ? x : 0 in sum1).  A column of a tracer without a negative value is not written at all.  The tracers are taken four to a
+ * launch, sharing the reads of dp.  FV3_ERR_ARG (a message, nothing launched): n_tracers < 0, a null list with n_tracers > 0, a
+ * null or 2-D dp, a tracer that does not match the context layout, dp among the tracers, a tracer given twice.
+ * FV3_ERR_UNSUPPORTED: nz < 2.  n_tracers == 0: FV3_OK, nothing launched. */
+int fv3_fillz(fv3_ctx *, int n_tracers, const fv3_field *const *tracers, const fv3_field *dp, void *stream);
 
 /* CubedToLatLon (the last operator of fv_dynamics: FV3 fv_grid_utils.F90 c2l_ord4 / c2l_ord2; pyFV3 CubedToLatLon, savepoint
  * FVDynamics-Out ua / va [REF tests/savepoint/thresholds/fv_dynamics.yaml]).  D-grid u, v -> ua, va on the compute cells in earth

@@ -101,6 +101,8 @@ class AcousticDynamicsConfig:
     breed_vortex_inline: bool = False
     # CubedToLatLon at the end of fv_dynamics: 4 (c2l_ord4) unless the yaml says otherwise, or 2 (c2l_ord2)
     c2l_ord: int = 4
+    # negative tracer means are filled in the vertical (fillz) at the end of the remap; FV3's namelist default is off
+    fill: bool = False
 
     def validate(self):
         """The kernels are specialised like the reference configs; anything else fails loudly."""

@@ -4,7 +4,8 @@
 // kord_tm -9, kord_mt / kord_tr / kord_wz 9, consv_te 0: driver/examples/configs/baroclinic_c12.yaml:45,65-68].
 // Restated from fv_mapz.F90 (map_scalar / map1_ppm with cs_profile, kord 9); configuration of the reference configs:
 // non-hydrostatic, T_v remapped in log(p), moist-cappa pkz with the cappa field given, no energy fixer, no saturation
-// adjustment, no fillz, omga untouched.
+// adjustment, omga untouched.  The vertical filling of negative tracer means (`fill: true`) is fv3_fillz (fv3_fillz.hip), called
+// right after this entry with the remapped tracers and delp.
 //
 // A thread owns a column (i fastest: every level access of a wave is one coalesced row).  What a column needs beyond
 // O(1) registers are the edge values of the parabolas (a tridiagonal solve in k): two scratch fields (the elimination factors

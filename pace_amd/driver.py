@@ -4,7 +4,8 @@
 
 It reproduces the reference's time loop for ``dycore_only: true`` + ``disable_step_physics: true``
 [REF driver/pace/driver/driver.py:627-662]: one timer entry per model step, a step being ``k_split`` x
-[AcousticDynamics (+ tracer advection with ``--tracers N``, + the vertical remap with ``--remap``)], and writes
+[AcousticDynamics (+ tracer advection with ``--tracers N``, + the vertical remap with ``--remap``, +
+the vertical filling of negative tracer values at the end of the remap with ``dycore_config.fill: true`` or ``--fill on``)], and writes
 the per-step times in the layout the reference's performance collector uses
 (``{"times": {<timer>: {"hits": n, "times": [[...per step...] per rank]}}}``, timers ``mainloop``, ``DynCore``,
 ``TracerAdvection``, ``Remapping`` [REF tests/main/driver/test_driver.py:77-121]).  With ``--tracers N --remap`` the step is the
@@ -103,6 +104,16 @@ def filter_diagnostics(block, known):
     return block, dropped
 
 
+def resolve_fill(option: str, dycore_config: dict, tracers: int, remap: bool) -> bool:
+    """Whether the step fills negative tracer values in the vertical (``fillz`` at the end of the remap): the yaml's
+    ``dycore_config.fill`` (absent = false, FV3's namelist default) unless ``--fill on|off`` overrides it; without ``--remap`` or
+    without tracers there is nothing to fill and the key is ignored."""
+    if option not in ("yaml", "on", "off"):
+        raise ValueError(f"--fill {option!r}: yaml, on or off")
+    want = bool(dycore_config.get("fill", False)) if option == "yaml" else option == "on"
+    return bool(want and tracers and remap)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("config")
@@ -113,6 +124,8 @@ def main(argv=None):
     ap.add_argument("--save-restart", default=None, help="write restart_dycore_state_<rank>.nc files there after the last step [REF state.py:114-123]")
     ap.add_argument("--tracers", type=int, default=0, help="advect N synthetic tracers after every acoustic call (TracerAdvection, hord_tr from the yaml)")
     ap.add_argument("--remap", action="store_true", help="Lagrangian-to-Eulerian remap after every acoustic call (with --tracers: the body of DynamicalCore.step_dynamics)")
+    ap.add_argument("--fill", choices=("yaml", "on", "off"), default="yaml",
+                    help="fill negative tracer values in the vertical at the end of the remap (needs --tracers N --remap): yaml = dycore_config.fill (absent: off); on / off override it")
     ap.add_argument("--latlon-winds", action="store_true",
                     help="CubedToLatLon at the end of every step (c2l_ord from the yaml, default 4): state ua / va become the eastward / northward cell-centre winds")
     ap.add_argument("--diagnostics-path", default=None, help="directory of the diagnostics (overrides diagnostics_config.path of the yaml)")
@@ -132,8 +145,11 @@ def main(argv=None):
         say(f"backend {run['backend']!r} requested by the yaml -> running 'hip:gfx950' (the only backend of this build)")
     if not (run["dycore_only"] and run["disable_step_physics"]):
         say("physics is outside this build: running the dycore-only loop")
-    say("step = k_split x [acoustic dynamics" + (f", advection of {a.tracers} tracers" if a.tracers else "") + (", vertical remap" if a.remap else "") + "]" + (", then CubedToLatLon" if a.latlon_winds else "")
+    fill = resolve_fill(a.fill, dy, a.tracers, a.remap)
+    say("step = k_split x [acoustic dynamics" + (f", advection of {a.tracers} tracers" if a.tracers else "") + (", vertical remap" if a.remap else "") + (" + fillz" if fill else "") + "]" + (", then CubedToLatLon" if a.latlon_winds else "")
         + ("" if (a.tracers and a.remap) else "  (--tracers N --remap add the rest of step_dynamics)"))
+    say(f'"fill": {str(fill).lower()}' + ("" if a.fill == "yaml" else f" (--fill {a.fill})")
+        + ("  (ignored without --tracers N --remap)" if (not fill and (a.fill == "on" or (a.fill == "yaml" and dy.get("fill")))) else ""))
     if run["init"] == "analytic" and str(run["case"]).startswith("baroclinic"):
         init = "baroclinic"
         say("initialization: JW2006 baroclinic wave (pace_amd.init.baroclinic_state; restated from the paper, see its docstring)")
@@ -154,8 +170,8 @@ def main(argv=None):
     dtype = torch.float64 if a.precision == 64 else torch.float32
     kw = {k: dy[k] for k in ("k_split", "n_split") if k in dy}
     h = DycoreHarness(nx_tile=run["nx_tile"], nz=run["nz"], layout=run["layout"], dt_atmos=run["dt_atmos"], world_size=world, proc=rank,
-                      device=f"cuda:{local_rank}", dtype=dtype, verbose=(rank == 0), init=init, config_overrides={k: v for k, v in dy.items() if k not in ("k_split", "n_split")},
-                      n_tracers=a.tracers, hord_tr=int(dy.get("hord_tr", 8)), remap=a.remap, latlon_winds=a.latlon_winds, **kw)
+                      device=f"cuda:{local_rank}", dtype=dtype, verbose=(rank == 0), init=init, config_overrides={k: v for k, v in dy.items() if k not in ("k_split", "n_split", "fill")},
+                      n_tracers=a.tracers, hord_tr=int(dy.get("hord_tr", 8)), remap=a.remap, fill=fill, latlon_winds=a.latlon_winds, **kw)
     if run["device_sync"]:
         h.sf.set_device_sync(True)
     if a.restart:
@@ -238,7 +254,7 @@ def main(argv=None):
         sdpd = run["dt_atmos"] / mean
         out = a.out or f"{run['experiment']}_fv3_mi355x.json"
         json.dump({"setup": {"experiment": run["experiment"], "nx_tile": run["nx_tile"], "nz": run["nz"], "layout": list(run["layout"]), "dt_atmos": run["dt_atmos"],
-                             "k_split": h.cfg.k_split, "n_split": h.cfg.n_split, "n_gpus": world, "backend": "hip:gfx950", "dycore_only": True, "acoustic_only": not (a.tracers or a.remap), "tracers": a.tracers, "remap": bool(a.remap), "finite": ok,
+                             "k_split": h.cfg.k_split, "n_split": h.cfg.n_split, "n_gpus": world, "backend": "hip:gfx950", "dycore_only": True, "acoustic_only": not (a.tracers or a.remap), "tracers": a.tracers, "remap": bool(a.remap), "fill": fill, "finite": ok,
                              "note": ("a step here is k_split AcousticDynamics calls; the reference's dycore_only mainloop (DynamicalCore.step_dynamics) also runs tracer "
                                       "advection and the Lagrangian-to-Eulerian remap (--tracers N --remap add them): not comparable with the reference's 'mainloop' timer")
                              if not (a.tracers and a.remap) else

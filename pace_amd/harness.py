@@ -5,7 +5,8 @@ the hot path with ``dycore_only: true, disable_step_physics: true``
 One "step" = ``k_split`` calls of AcousticDynamics, timed like the reference ("mainloop" timer, first step dropped
 [REF .jenkins/print_performance_number.py:13-14]).  The headline workload is the acoustic loop alone; ``n_tracers`` adds the
 sub-cycled tracer advection after every acoustic call and ``remap`` the Lagrangian-to-Eulerian remap after that (SURVEY §8f-3:
-together the body of ``DynamicalCore.step_dynamics``; no physics, no moist thermodynamics); ``latlon_winds`` the CubedToLatLon that
+together the body of ``DynamicalCore.step_dynamics``; no physics, no moist thermodynamics), ``fill`` the vertical filling of negative
+tracer values at the end of the remap (the namelist's ``fill``); ``latlon_winds`` the CubedToLatLon that
 ends ``fv_dynamics`` (eastward / northward ``ua``, ``va``).
 """
 from __future__ import annotations
@@ -61,6 +62,7 @@ class DycoreHarness:
         n_tracers: int = 0,
         hord_tr: int = 8,
         remap: bool = False,
+        fill: bool = False,
         init_data=None,
         ak=None,
         bk=None,
@@ -68,10 +70,12 @@ class DycoreHarness:
         latlon_winds: bool = False,
         _testing_token=None,
     ):
+        if fill and not remap:
+            raise ValueError("fill=True needs remap=True: the vertical filling of negative tracer values is the last tracer step of the remap")
         self.c = get_constants()
         self.part = CubedSpherePartitioner(nx_tile, tuple(layout))
         self.cfg = AcousticDynamicsConfig(npx=nx_tile + 1, npy=nx_tile + 1, npz=nz, layout=tuple(layout), dt_atmos=dt_atmos, k_split=k_split, n_split=n_split,
-                                          **(config_overrides or {}))
+                                          **{**(config_overrides or {}), "fill": bool(fill)})
         self.layout = Layout(self.part, world_size, proc)
         self.layout.group = group
         self.layout.loopback = bool(loopback)  # this process plays `proc` of `world_size` alone, its messages looped back (timing runs)
@@ -134,7 +138,7 @@ class DycoreHarness:
         if remap:
             from .stencils import LagrangianToEulerian
 
-            self.remap = LagrangianToEulerian(self.sf, self.sf.quantity_factory, self.grids)
+            self.remap = LagrangianToEulerian(self.sf, self.sf.quantity_factory, self.grids, fill=fill)
             self.ps = self.sf.quantity_factory.zeros(("x", "y"), "Pa")
         # CubedToLatLon once per step, after the k_split loop (where fv_dynamics runs it): state.ua / state.va become the eastward /
         # northward cell-centre winds.  Off by default: without it ua / va keep what the last c_sw left (local A-grid components).

@@ -165,6 +165,7 @@ _PROTOS = {
     "fv3_tracer_2d_1l_cmax": (C.c_int, [C.c_void_p, F, F, P(C.c_double), _S]),
     "fv3_tracer_2d_1l": (C.c_int, [C.c_void_p, _I, P(F), F, F, F, F, F, _I, _I, C.c_void_p, _S]),
     "fv3_remap": (C.c_int, [C.c_void_p, _I, P(F)] + [F] * 13 + [_S]),
+    "fv3_fillz": (C.c_int, [C.c_void_p, _I, P(F), F, _S]),
     "fv3_cubed_to_latlon": (C.c_int, [C.c_void_p, _I] + [F] * 8 + [_S]),
     "fv3_diag_pack": (C.c_int, [C.c_void_p, F, _I, _I, _I, _I, C.c_void_p, C.c_long, _S]),
     "fv3_diag_column_integral": (C.c_int, [C.c_void_p, F, F, C.c_void_p, C.c_long, _S]),

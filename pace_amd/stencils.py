@@ -259,10 +259,36 @@ class TracerAdvection(_Op):
             raise _lib.Fv3Error(f"fv3_tracer_2d_1l failed ({st}): " + sf.lib.fv3_last_error(sf.ctx).decode())
 
 
+class FillNegativeTracerValues(_Op):
+    """``fillz`` (FV3 ``fv_fill.F90``; the pyFV3 operator of this name): negative layer means of the tracers are filled, column by
+    column, with mass borrowed from the neighbouring layers and -- where that does not suffice -- by rescaling the positive
+    part of the column (``fv3_fillz`` in include/fv3_mi355x.h holds the algorithm).  In place on the compute cells; ``dp2`` (the
+    layer thickness the mixing ratios refer to) is only read.  Call as the reference's ``fillz(dp2, tracers)`` with ``tracers``
+    a dict of quantities."""
+
+    def __call__(self, dp2, tracers):
+        import ctypes as C
+
+        from . import lib as _lib
+
+        qs = list(tracers.values()) if tracers else []
+        arr = (_lib.F * max(len(qs), 1))(*[C.pointer(q.field) for q in qs])
+        st = self.sf.lib.fv3_fillz(self.sf.ctx, len(qs), arr, dp2.fref, self.sf.stream_handle)
+        if st != 0:
+            raise _lib.Fv3Error(f"fv3_fillz failed ({st}): " + self.sf.lib.fv3_last_error(self.sf.ctx).decode())
+
+
 class LagrangianToEulerian(_Op):
     """The vertical remap that closes ``DynamicalCore.step_dynamics`` (reference operator pyFV3
     ``LagrangianToEulerian``, savepoint ``Remapping`` [REF tests/savepoint/thresholds/fv_dynamics.yaml:227-326]).  Call with the
-    state's quantities; everything is remapped in place (see ``fv3_remap`` in include/fv3_mi355x.h for the configuration)."""
+    state's quantities; everything is remapped in place (see ``fv3_remap`` in include/fv3_mi355x.h for the configuration).
+    ``fill`` (the namelist's ``fill``, default off): after the remap the negative tracer means are filled in the vertical
+    (:class:`FillNegativeTracerValues` with the Eulerian ``delp``) on the same stream, where the reference runs its ``fillz``."""
+
+    def __init__(self, stencil_factory, quantity_factory=None, grid_data=None, *args, fill: bool = False, **kw):
+        super().__init__(stencil_factory, quantity_factory, grid_data, *args, **kw)
+        self.fill = bool(fill)
+        self._fillz = FillNegativeTracerValues(stencil_factory, quantity_factory, grid_data) if self.fill else None
 
     def __call__(self, tracers, pt, delp, delz, peln, pe, pk, pkz, u, v, w, cappa, ps, wsd):
         import ctypes as C
@@ -275,6 +301,8 @@ class LagrangianToEulerian(_Op):
                                    ps.fref, wsd.fref, self.sf.stream_handle)
         if st != 0:
             raise _lib.Fv3Error(f"fv3_remap failed ({st}): " + self.sf.lib.fv3_last_error(self.sf.ctx).decode())
+        if self._fillz is not None and qs:
+            self._fillz(delp, tracers)  # delp is the Eulerian layer thickness by now: the reference's dp2
 
 
 class CubedToLatLon(_Op):
