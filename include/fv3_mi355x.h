@@ -379,6 +379,33 @@ int fv3_remap(fv3_ctx *, int n_tracers, const fv3_field *const *tracers, const f
  * FV3_ERR_UNSUPPORTED: nz < 2.  n_tracers == 0: FV3_OK, nothing launched. */
 int fv3_fillz(fv3_ctx *, int n_tracers, const fv3_field *const *tracers, const fv3_field *dp, void *stream);
 
+/* ---- the thermodynamic bookends of DynamicalCore.step_dynamics (fv3_thermo.hip) ---------------------------------------------
+ * state.pt is a temperature (K) before and after a model step [REF driver/pace/driver/driver.py:494-504, 639-644]; the acoustic
+ * loop, the tracer advection and the remap work on T_v / pkz.  Both entries work on the compute cells 1..nx x 1..ny, levels
+ * 0 .. nz-1 of every sub-domain, in the build's Real, every product and quotient rounded on its own, left to right; halo cells,
+ * the pad level nz and the fields that are only read are never written.  exp / log are the calls of fv3_remap's kernels.
+ *   rrg = (Real)(-rdgas / grav), zvir = (Real)(rvgas / rdgas - 1), fac = (1 + zq) * (1 - q_con) with zq = zvir * qvapor, or
+ *   zq = 0 where qvapor is NULL (bitwise what a qvapor field of zeros gives).  q_con and cappa are fields: what derives them
+ *   (moist_cv) is outside this library.
+ *
+ * fv3_pt_from_temperature, the preamble of fv_dynamics (pt: T in, the loop's form out; pkz: out):
+ *   tv = pt * fac;  pz = exp(cappa * log(rrg * delp / delz * tv));  pkz = pz;  pt = tv / pz
+ *
+ * fv3_temperature_from_pt, the last-step conversion of the remap and the omga / ps diagnoses (pt: the loop's form in, T out):
+ *   recompute_pkz == 0:  tv = pt * pkz                       (FV3's own form: valid where pkz belongs to pt, i.e. after a remap)
+ *   recompute_pkz == 1:  tv = pt * exp(cappa / (1 - cappa) * log(rrg * delp / delz * pt));
+ *                        pkz = exp(cappa * log(rrg * delp / delz * tv))     (pkz is rebuilt from the state, as fv3_remap does)
+ *   pt = tv / fac;  omga = delp / delz * w  where omga is not NULL;  ps = pe[.., nz]  where ps is not NULL (a 2-D field)
+ *
+ * FV3_ERR_ARG (a message, nothing launched, no field changed): a null context, a null or wrongly shaped field (ps must be 2-D,
+ * every other field 3-D), recompute_pkz other than 0 / 1, pt / pkz / omga / ps given twice, one of them also given as a field
+ * that is only read (delp, delz, q_con, cappa, qvapor, w, pe). */
+int fv3_pt_from_temperature(fv3_ctx *, const fv3_field *pt, const fv3_field *pkz, const fv3_field *delp, const fv3_field *delz,
+                            const fv3_field *q_con, const fv3_field *cappa, const fv3_field *qvapor, void *stream);
+int fv3_temperature_from_pt(fv3_ctx *, const fv3_field *pt, const fv3_field *pkz, const fv3_field *delp, const fv3_field *delz,
+                            const fv3_field *q_con, const fv3_field *cappa, const fv3_field *qvapor, const fv3_field *w,
+                            const fv3_field *omga, const fv3_field *pe, const fv3_field *ps, int recompute_pkz, void *stream);
+
 /* CubedToLatLon (the last operator of fv_dynamics: FV3 fv_grid_utils.F90 c2l_ord4 / c2l_ord2; pyFV3 CubedToLatLon, savepoint
  * FVDynamics-Out ua / va [REF tests/savepoint/thresholds/fv_dynamics.yaml]).  D-grid u, v -> ua, va on the compute cells in earth
  * coordinates (eastward, northward).  order: c2l_ord, 4 (the reference's default) or 2.  a11 .. a22: the cell-centre rotation

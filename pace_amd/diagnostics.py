@@ -131,8 +131,11 @@ class DiagnosticsConfig:
             monitor = ZarrMonitor(self.path, harness.layout, start_time=start_time)
         else:
             monitor = NetCDFMonitor(self.path, harness.layout, time_chunk_size=self.time_chunk_size, start_time=start_time)
+        # a harness that steps through DynamicalCore (temperature=True) also holds the surface pressure its last step diagnosed
+        dycore = getattr(harness, "dycore", None)
+        extra = {"ps": dycore.ps} if dycore is not None else None
         return MonitorDiagnostics(monitor, self.names, self.derived_names, self.z_select, state=harness.state, tracers=harness.tracers, stencil_factory=harness.sf,
-                                  grids=harness.grids)
+                                  grids=harness.grids, extra=extra)
 
 
 def diagnostics_factory(harness, config: Optional[DiagnosticsConfig] = None, start_time=None) -> Diagnostics:
@@ -153,7 +156,7 @@ class _Var:
 class MonitorDiagnostics(Diagnostics):
     """Diagnostics that save to a monitor of ``pace_amd.monitor`` (module docstring: what is packed, copied and checked, and when)."""
 
-    def __init__(self, monitor, names, derived_names, z_select, state=None, tracers=None, stencil_factory=None, grids=None):
+    def __init__(self, monitor, names, derived_names, z_select, state=None, tracers=None, stencil_factory=None, grids=None, extra=None):
         import torch
 
         from .restart import _UNITS
@@ -167,6 +170,7 @@ class MonitorDiagnostics(Diagnostics):
         self.z_select = list(z_select)
         self.state = state
         self.tracers = dict(tracers or {})
+        self.extra = dict(extra or {})  # fields held beside the state ({"ps": DynamicalCore.ps})
         self.sf = stencil_factory
         self.grids = grids
         self._pack = FieldPack(stencil_factory)
@@ -208,13 +212,15 @@ class MonitorDiagnostics(Diagnostics):
         return [v.name for v in self._plan]
 
     def _known(self) -> List[str]:
-        return STATE_NAMES + ["phis"] + list(self.tracers)
+        return STATE_NAMES + ["phis"] + list(self.tracers) + list(self.extra)
 
     def _resolve(self, name: str, state) -> Quantity:
         if name in STATE_NAMES or name == "phis":
             return getattr(state, name)
         if name in self.tracers:
             return self.tracers[name]
+        if name in self.extra:
+            return self.extra[name]
         raise ValueError(f"diagnostics: unknown variable {name!r}; this build's state holds: {', '.join(self._known())}")
 
     def _stream(self):

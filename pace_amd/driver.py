@@ -5,7 +5,9 @@
 It reproduces the reference's time loop for ``dycore_only: true`` + ``disable_step_physics: true``
 [REF driver/pace/driver/driver.py:627-662]: one timer entry per model step, a step being ``k_split`` x
 [AcousticDynamics (+ tracer advection with ``--tracers N``, + the vertical remap with ``--remap``, +
-the vertical filling of negative tracer values at the end of the remap with ``dycore_config.fill: true`` or ``--fill on``)], and writes
+the vertical filling of negative tracer values at the end of the remap with ``dycore_config.fill: true`` or ``--fill on``)] -- with
+``--temperature`` (needs ``--remap``) the step is ``DynamicalCore.step_dynamics``: ``pt`` is a temperature in K before and after it,
+``omga`` and ``ps`` are diagnosed, and the start-up line and the json ``setup`` say ``"pt": "temperature"`` (otherwise ``"loop"``) -- and writes
 the per-step times in the layout the reference's performance collector uses
 (``{"times": {<timer>: {"hits": n, "times": [[...per step...] per rank]}}}``, timers ``mainloop``, ``DynCore``,
 ``TracerAdvection``, ``Remapping`` [REF tests/main/driver/test_driver.py:77-121]).  With ``--tracers N --remap`` the step is the
@@ -26,7 +28,7 @@ Diagnostics [REF driver/pace/driver/driver.py:551-552, 588-611, 702-705]: with a
 (``pace_amd.diagnostics.DiagnosticsConfig``) the driver stores the initial state when ``output_initial_state`` is set, stores after
 every ``output_frequency``-th step -- outside the step clock -- and ends with ``store_grid`` and ``cleanup``.  Names of the block that
 this build's state does not hold (``qvapor`` ... ``qgraupel``, ``ps``: the reference's yamls ask for them) are dropped and reported in
-one line.  ``--diagnostics-path DIR`` overrides the block's ``path``, ``--no-diagnostics`` turns the block off.  Without a block
+one line; with ``--temperature`` ``ps`` is known and stored from ``DynamicalCore.ps``.  ``--diagnostics-path DIR`` overrides the block's ``path``, ``--no-diagnostics`` turns the block off.  Without a block
 nothing changes.
 """
 from __future__ import annotations
@@ -128,9 +130,13 @@ def main(argv=None):
                     help="fill negative tracer values in the vertical at the end of the remap (needs --tracers N --remap): yaml = dycore_config.fill (absent: off); on / off override it")
     ap.add_argument("--latlon-winds", action="store_true",
                     help="CubedToLatLon at the end of every step (c2l_ord from the yaml, default 4): state ua / va become the eastward / northward cell-centre winds")
+    ap.add_argument("--temperature", action="store_true",
+                    help="step through DynamicalCore.step_dynamics (needs --remap): state pt is a temperature in K before and after every step, omga = delp / delz * w and ps are diagnosed")
     ap.add_argument("--diagnostics-path", default=None, help="directory of the diagnostics (overrides diagnostics_config.path of the yaml)")
     ap.add_argument("--no-diagnostics", action="store_true", help="ignore the yaml's diagnostics_config block")
     a = ap.parse_args(argv)
+    if a.temperature and not a.remap:
+        sys.exit("--temperature needs --remap: the conversion back to temperature is the last step of the remap")
     run, dy, ignored = load_config(a.config)
 
     import torch
@@ -146,10 +152,12 @@ def main(argv=None):
     if not (run["dycore_only"] and run["disable_step_physics"]):
         say("physics is outside this build: running the dycore-only loop")
     fill = resolve_fill(a.fill, dy, a.tracers, a.remap)
+    pt_form = "temperature" if a.temperature else "loop"
     say("step = k_split x [acoustic dynamics" + (f", advection of {a.tracers} tracers" if a.tracers else "") + (", vertical remap" if a.remap else "") + (" + fillz" if fill else "") + "]" + (", then CubedToLatLon" if a.latlon_winds else "")
         + ("" if (a.tracers and a.remap) else "  (--tracers N --remap add the rest of step_dynamics)"))
     say(f'"fill": {str(fill).lower()}' + ("" if a.fill == "yaml" else f" (--fill {a.fill})")
         + ("  (ignored without --tracers N --remap)" if (not fill and (a.fill == "on" or (a.fill == "yaml" and dy.get("fill")))) else ""))
+    say(f'"pt": "{pt_form}"' + ("  (DynamicalCore.step_dynamics: temperature in K in and out, omga and ps diagnosed)" if a.temperature else "  (the acoustic loop's T_v / pkz; --temperature --remap: temperature in K)"))
     if run["init"] == "analytic" and str(run["case"]).startswith("baroclinic"):
         init = "baroclinic"
         say("initialization: JW2006 baroclinic wave (pace_amd.init.baroclinic_state; restated from the paper, see its docstring)")
@@ -171,12 +179,16 @@ def main(argv=None):
     kw = {k: dy[k] for k in ("k_split", "n_split") if k in dy}
     h = DycoreHarness(nx_tile=run["nx_tile"], nz=run["nz"], layout=run["layout"], dt_atmos=run["dt_atmos"], world_size=world, proc=rank,
                       device=f"cuda:{local_rank}", dtype=dtype, verbose=(rank == 0), init=init, config_overrides={k: v for k, v in dy.items() if k not in ("k_split", "n_split", "fill")},
-                      n_tracers=a.tracers, hord_tr=int(dy.get("hord_tr", 8)), remap=a.remap, fill=fill, latlon_winds=a.latlon_winds, **kw)
+                      n_tracers=a.tracers, hord_tr=int(dy.get("hord_tr", 8)), remap=a.remap, fill=fill, latlon_winds=a.latlon_winds, temperature=a.temperature, **kw)
     if run["device_sync"]:
         h.sf.set_device_sync(True)
     if a.restart:
         from . import restart
 
+        try:
+            restart.check_pt_form(h.layout.local_ranks, a.restart, a.temperature)
+        except ValueError as e:
+            sys.exit(f"--restart: {e}")
         restart.load_state(h.state, h.layout.local_ranks, a.restart, extra=h.tracers)
         h.dyn._bind(h.state)
         say(f"state loaded from {a.restart}")
@@ -187,7 +199,7 @@ def main(argv=None):
 
     diagnostics = NullDiagnostics()
     if run["diagnostics_config"] and not a.no_diagnostics:
-        block, dropped = filter_diagnostics(run["diagnostics_config"], STATE_NAMES + ["phis"] + list(h.tracers))
+        block, dropped = filter_diagnostics(run["diagnostics_config"], STATE_NAMES + ["phis"] + list(h.tracers) + (["ps"] if a.temperature else []))
         if a.diagnostics_path:
             block["path"] = a.diagnostics_path
         if dropped:
@@ -232,7 +244,7 @@ def main(argv=None):
     if a.save_restart:
         from . import restart
 
-        restart.save_state(h.state, h.layout.local_ranks, a.save_restart, extra=h.tracers)
+        restart.save_state(h.state, h.layout.local_ranks, a.save_restart, extra=h.tracers, **({"pt_form": restart.PT_TEMPERATURE} if a.temperature else {}))
         say(f"restart files written to {a.save_restart}")
     # per reference rank (the ranks a process owns step together: they share its clocks)
     local = {r: {n: [t.get(n, 0.0) for t in times_per_step] for n in times_per_step[0]} for r in h.layout.local_ranks}
@@ -254,7 +266,7 @@ def main(argv=None):
         sdpd = run["dt_atmos"] / mean
         out = a.out or f"{run['experiment']}_fv3_mi355x.json"
         json.dump({"setup": {"experiment": run["experiment"], "nx_tile": run["nx_tile"], "nz": run["nz"], "layout": list(run["layout"]), "dt_atmos": run["dt_atmos"],
-                             "k_split": h.cfg.k_split, "n_split": h.cfg.n_split, "n_gpus": world, "backend": "hip:gfx950", "dycore_only": True, "acoustic_only": not (a.tracers or a.remap), "tracers": a.tracers, "remap": bool(a.remap), "fill": fill, "finite": ok,
+                             "k_split": h.cfg.k_split, "n_split": h.cfg.n_split, "n_gpus": world, "backend": "hip:gfx950", "dycore_only": True, "acoustic_only": not (a.tracers or a.remap), "tracers": a.tracers, "remap": bool(a.remap), "fill": fill, "pt": pt_form, "finite": ok,
                              "note": ("a step here is k_split AcousticDynamics calls; the reference's dycore_only mainloop (DynamicalCore.step_dynamics) also runs tracer "
                                       "advection and the Lagrangian-to-Eulerian remap (--tracers N --remap add them): not comparable with the reference's 'mainloop' timer")
                              if not (a.tracers and a.remap) else

@@ -1,0 +1,110 @@
+"""``DynamicalCore`` -- the public entry of the path: ``DynamicalCore(...).step_dynamics(state, timer)``, the one call through
+which the reference reaches the dynamical core [REF driver/pace/driver/driver.py:494-504, 639-644].
+
+The contract of the call is the reference's: ``state.pt`` holds the temperature in K before and after a step.  Inside the step
+
+1. :class:`~pace_amd.stencils.TemperatureToPotential` takes ``pt`` to the form the acoustic loop transports (``T_v / pkz``) and
+   rebuilds ``pkz``,
+2. ``k_split`` times: the ``dp1`` copy, :class:`~pace_amd.dyn_core.AcousticDynamics` ("DynCore"), the tracer halo update and
+   :class:`~pace_amd.stencils.TracerAdvection` ("TracerAdvection"), :class:`~pace_amd.stencils.LagrangianToEulerian` with the
+   vertical filling where ``config.fill`` asks for it ("Remapping") -- the sequence of ``DycoreHarness.step``,
+3. :class:`~pace_amd.stencils.PotentialToTemperature` takes ``pt`` back to K with the ``pkz`` the last remap left, diagnoses
+   ``state.omga = delp / delz * w`` and the surface pressure ``DynamicalCore.ps``,
+4. :class:`~pace_amd.stencils.CubedToLatLon`, where asked ("CubedToLatLon").
+
+``q_con`` and ``cappa`` are fields of the state: what derives them from the water species (``moist_cv``) is outside this build, as
+are the saturation adjustment and the physics coupling.  Every buffer (``dp1``, ``ps``, the operators' own) is allocated by the
+constructor; ``step_dynamics`` allocates nothing.
+"""
+from __future__ import annotations
+
+from typing import Dict, Optional
+
+from . import stencils as st
+from .constants import X_DIM, Y_DIM, Z_DIM
+from .dyn_core import AcousticDynamics, DycoreState
+from .quantity import Quantity
+
+
+class DynamicalCore:
+    def __init__(
+        self,
+        comm,
+        grid_data,
+        stencil_factory,
+        quantity_factory=None,
+        damping_coefficients=None,
+        config=None,
+        timestep=None,
+        phis: Optional[Quantity] = None,
+        state: Optional[DycoreState] = None,
+        checkpointer=None,
+        *,
+        tracers: Optional[Dict[str, Quantity]] = None,
+        hord_tr: int = 8,
+        vapor: Optional[str] = None,
+        cubed_to_latlon: bool = True,
+    ):
+        """Arguments as the reference's call.  ``comm``: a :class:`pace_amd.halo.Layout` (None: every rank in this process);
+        ``timestep``: the model step ``dt_atmos`` in seconds or as a ``timedelta`` (None: ``config.dt_atmos``); ``tracers``:
+        ``{name: Quantity}`` advected and remapped with the step (may be empty); ``vapor``: the name of the tracer that is the
+        specific humidity (None: a dry conversion between temperature and virtual temperature); ``hord_tr``: the tracers'
+        transport scheme; ``cubed_to_latlon``: end the step with the eastward / northward ``ua``, ``va``."""
+        sf = stencil_factory
+        qf = quantity_factory or sf.quantity_factory
+        self.sf, self.qf = sf, qf
+        self.config = (config or sf.config).validate()
+        if timestep is None:
+            timestep = self.config.dt_atmos
+        self.timestep = float(timestep.total_seconds()) if hasattr(timestep, "total_seconds") else float(timestep)
+        self.tracers = dict(tracers or {})
+        if vapor is not None and vapor not in self.tracers:
+            raise ValueError(f"vapor={vapor!r} is not among the tracers ({', '.join(self.tracers) or 'none'})")
+        self.vapor = vapor
+        self.fill = bool(getattr(self.config, "fill", False))
+        self.acoustic_dynamics = AcousticDynamics(comm, grid_data, sf, qf, damping_coefficients, config=self.config, phis=phis, state=state, checkpointer=checkpointer)
+        self.layout = self.acoustic_dynamics.layout
+        cell = (X_DIM, Y_DIM, Z_DIM)
+        self.tracer_advection = None
+        self.dp1 = None
+        self._tracer_halo = None
+        if self.tracers:
+            self.dp1 = qf.zeros(cell, "Pa")
+            self.tracer_advection = st.TracerAdvection(sf, qf, st.FiniteVolumeTransport(sf, qf, grid_data, hord=hord_tr), grid_data, self.layout, self.tracers)
+            self._tracer_halo = self.acoustic_dynamics.halo.updater("cell", [(q,) for q in self.tracers.values()])
+        self.remap = st.LagrangianToEulerian(sf, qf, grid_data, fill=self.fill)
+        self.ps = qf.zeros((X_DIM, Y_DIM), "Pa")
+        self.temperature_to_potential = st.TemperatureToPotential(sf, qf, grid_data)
+        self.potential_to_temperature = st.PotentialToTemperature(sf, qf, grid_data)
+        self.cubed_to_latlon = st.CubedToLatLon(sf, qf, grid_data, order=self.config.c2l_ord, comm=self.layout) if cubed_to_latlon else None
+
+    @property
+    def qvapor(self) -> Optional[Quantity]:
+        return None if self.vapor is None else self.tracers[self.vapor]
+
+    def step_dynamics(self, state: DycoreState, timer=None):
+        """One model step: ``state.pt`` is a temperature (K) on entry and on return.  ``timer`` (pace_amd.timer.Timer): the
+        reference's clocks "DynCore", "TracerAdvection", "Remapping", "CubedToLatLon" [REF tests/main/driver/test_driver.py:77-121]."""
+        from .timer import NullTimer
+
+        timer = timer or NullTimer()
+        s, dyn, tracers, qv = state, self.acoustic_dynamics, self.tracers, self.qvapor
+        self.temperature_to_potential(s.pt, s.pkz, s.delp, s.delz, s.q_con, s.cappa, qv)
+        k_split = self.config.k_split
+        dt = self.timestep / k_split
+        for k in range(k_split):
+            if tracers:
+                self.dp1.storage.copy_(s.delp.storage)  # the air mass the accumulated mass fluxes start from
+            with timer.clock("DynCore"):
+                dyn(s, dt, n_map=k + 1)
+            if tracers:
+                with timer.clock("TracerAdvection"):
+                    self._tracer_halo.update()
+                    self.tracer_advection(tracers, self.dp1, s.mfxd, s.mfyd, s.cxd, s.cyd)
+            with timer.clock("Remapping"):
+                self.remap(tracers, s.pt, s.delp, s.delz, s.peln, s.pe, s.pk, s.pkz, s.u, s.v, s.w, s.cappa, self.ps, dyn._wsd)
+        # the last-step conversion of the remap: pkz is the one the remap has just formed with these delp, delz and T_v
+        self.potential_to_temperature(s.pt, s.pkz, s.delp, s.delz, s.q_con, s.cappa, s.w, s.pe, qvapor=qv, omga=s.omga, ps=self.ps, recompute_pkz=False)
+        if self.cubed_to_latlon is not None:
+            with timer.clock("CubedToLatLon"):
+                self.cubed_to_latlon(s.u, s.v, s.ua, s.va)

@@ -7,7 +7,9 @@ One "step" = ``k_split`` calls of AcousticDynamics, timed like the reference ("m
 sub-cycled tracer advection after every acoustic call and ``remap`` the Lagrangian-to-Eulerian remap after that (SURVEY §8f-3:
 together the body of ``DynamicalCore.step_dynamics``; no physics, no moist thermodynamics), ``fill`` the vertical filling of negative
 tracer values at the end of the remap (the namelist's ``fill``); ``latlon_winds`` the CubedToLatLon that
-ends ``fv_dynamics`` (eastward / northward ``ua``, ``va``).
+ends ``fv_dynamics`` (eastward / northward ``ua``, ``va``); ``temperature`` (needs ``remap``) makes the step
+``DynamicalCore.step_dynamics`` (pace_amd/fv_dynamics.py): ``state.pt`` is then a temperature in K between steps, ``omga`` and ``ps`` are
+diagnosed, ``vapor`` names the tracer that is the specific humidity.
 """
 from __future__ import annotations
 
@@ -68,10 +70,16 @@ class DycoreHarness:
         bk=None,
         loopback: bool = False,
         latlon_winds: bool = False,
+        temperature: bool = False,
+        vapor: Optional[str] = None,
         _testing_token=None,
     ):
         if fill and not remap:
             raise ValueError("fill=True needs remap=True: the vertical filling of negative tracer values is the last tracer step of the remap")
+        if temperature and not remap:
+            raise ValueError("temperature=True needs remap=True: the conversion back to temperature is the last step of the remap")
+        if vapor is not None and not temperature:
+            raise ValueError("vapor names the specific-humidity tracer of the temperature conversion: it needs temperature=True")
         self.c = get_constants()
         self.part = CubedSpherePartitioner(nx_tile, tuple(layout))
         self.cfg = AcousticDynamicsConfig(npx=nx_tile + 1, npy=nx_tile + 1, npz=nz, layout=tuple(layout), dt_atmos=dt_atmos, k_split=k_split, n_split=n_split,
@@ -116,21 +124,28 @@ class DycoreHarness:
             del s
         if verbose:
             print(f"[harness] {init} state in {time.time() - t0:.1f}s", flush=True)
+        self.tracers = {}
+        self.temperature = bool(temperature)
+        self.dycore = None
+        self.cells_local = self.part.nx * self.part.ny * nz * len(self.grids)
+        self.cells_global = nx_tile * nx_tile * 6 * nz
+        if temperature:
+            self._make_tracers(n_tracers)
+            if vapor is not None and init == "restart":  # the specific humidity the restart's T_v was formed with
+                self._load_restart_tracer(vapor, init_data, "sphum")
+            self._init_temperature(vapor, hord_tr, latlon_winds)
+            return
         self.dyn = AcousticDynamics(self.layout, self.grids, self.sf, config=self.cfg, phis=self.state.phis, state=self.state)
         # shared D-grid interface winds must be single-valued across sub-domains (they are in any
         # physical state; the per-rank white noise of the synthetic recipe breaks it)
         if not loopback:
             self.dyn._updaters["interface_u__v"].update()
         # tracers advected after every acoustic call with the mass fluxes / Courant numbers it accumulated
-        self.tracers = {}
         if n_tracers:
             from .stencils import FiniteVolumeTransport, TracerAdvection
 
             qf = self.sf.quantity_factory
-            for t in range(n_tracers):
-                q = qf.zeros(("x", "y", "z"), "kg/kg")
-                q.storage.copy_(self.state.q_con.storage * (10.0 * (t + 1)) + 1.0e-3 * (t + 1))
-                self.tracers[f"tracer{t}"] = q
+            self._make_tracers(n_tracers)
             self.dp1 = qf.zeros(("x", "y", "z"), "Pa")
             self.tracer_advection = TracerAdvection(self.sf, qf, FiniteVolumeTransport(self.sf, qf, self.grids, hord=hord_tr), self.grids, self.layout, self.tracers)
             self._tracer_halo = self.dyn.halo.updater("cell", [(q,) for q in self.tracers.values()])
@@ -147,8 +162,47 @@ class DycoreHarness:
             from .stencils import CubedToLatLon
 
             self.cubed_to_latlon = CubedToLatLon(self.sf, self.sf.quantity_factory, self.grids, order=self.cfg.c2l_ord, comm=self.layout)
-        self.cells_local = self.part.nx * self.part.ny * nz * len(self.grids)
-        self.cells_global = nx_tile * nx_tile * 6 * nz
+
+    def _make_tracers(self, n_tracers):
+        qf = self.sf.quantity_factory
+        for t in range(n_tracers):
+            q = qf.zeros(("x", "y", "z"), "kg/kg")
+            q.storage.copy_(self.state.q_con.storage * (10.0 * (t + 1)) + 1.0e-3 * (t + 1))
+            self.tracers[f"tracer{t}"] = q
+
+    def _load_restart_tracer(self, name, data, key):
+        """Tracer ``name`` from the six-tile restart arrays (``data[key][tile][k, y, x]``), placed like the state's cell fields
+        (``pace_amd.init.restart_state``: the compute cells, everything else edge-replicated)."""
+        if name not in self.tracers:
+            raise ValueError(f"vapor={name!r} is not among the tracers ({', '.join(self.tracers) or 'none'})")
+        nh, nx, ny, nz = self.grids[0].n_halo, self.part.nx, self.part.ny, self.cfg.npz
+        for i, r in enumerate(self.layout.local_ranks):
+            ox, oy = self.part.origin(r)
+            a = np.transpose(np.asarray(data[key][self.part.tile_index(r)], dtype=np.float64), (2, 1, 0))[ox : ox + nx, oy : oy + ny, :nz]
+            self.tracers[name].set_numpy(np.pad(a, ((nh, nh + 1), (nh, nh + 1), (0, 1)), mode="edge"), i)
+
+    def _init_temperature(self, vapor, hord_tr, latlon_winds):
+        """temperature=True: the step is ``DynamicalCore.step_dynamics`` over the harness's own state and tracers, and the state
+        holds T between steps.  The core owns the operators and buffers the default harness builds itself; they are reachable
+        under the same names (``dyn``, ``remap``, ``ps``, ...)."""
+        from .fv_dynamics import DynamicalCore
+
+        self.dycore = DynamicalCore(self.layout, self.grids, self.sf, self.sf.quantity_factory, None, self.cfg, self.cfg.dt_atmos, self.state.phis, self.state,
+                                    tracers=self.tracers, hord_tr=hord_tr, vapor=vapor, cubed_to_latlon=latlon_winds)
+        d = self.dycore
+        self.dyn = d.acoustic_dynamics
+        if not self.layout.loopback:
+            self.dyn._updaters["interface_u__v"].update()
+        self.remap, self.ps, self.cubed_to_latlon = d.remap, d.ps, d.cubed_to_latlon
+        if self.tracers:
+            self.dp1, self.tracer_advection, self._tracer_halo = d.dp1, d.tracer_advection, d._tracer_halo
+        self.to_temperature()
+
+    def to_temperature(self):
+        """The state's ``pt`` from the loop's form ``T_v / pkz`` (what every ``init`` and a default-mode restart file hold) to the
+        temperature in K, ``pkz`` rebuilt from the state, ``ps`` from ``pe``; ``omga`` is not touched."""
+        s, d = self.state, self.dycore
+        d.potential_to_temperature(s.pt, s.pkz, s.delp, s.delz, s.q_con, s.cappa, s.w, s.pe, qvapor=d.qvapor, ps=d.ps, recompute_pkz=True)
 
     def step(self, timer=None):
         """One model step of the dycore-only driver: k_split acoustic-dynamics calls (each followed by tracer advection and the
@@ -158,6 +212,9 @@ class DycoreHarness:
         from .timer import NullTimer
 
         timer = timer or NullTimer()
+        if self.dycore is not None:  # temperature=True: pt is a temperature before and after the step
+            self.dycore.step_dynamics(self.state, timer)
+            return
         dt = self.cfg.dt_atmos / self.cfg.k_split
         for k in range(self.cfg.k_split):
             if self.tracers:

@@ -166,6 +166,8 @@ _PROTOS = {
     "fv3_tracer_2d_1l": (C.c_int, [C.c_void_p, _I, P(F), F, F, F, F, F, _I, _I, C.c_void_p, _S]),
     "fv3_remap": (C.c_int, [C.c_void_p, _I, P(F)] + [F] * 13 + [_S]),
     "fv3_fillz": (C.c_int, [C.c_void_p, _I, P(F), F, _S]),
+    "fv3_pt_from_temperature": (C.c_int, [C.c_void_p] + [F] * 7 + [_S]),
+    "fv3_temperature_from_pt": (C.c_int, [C.c_void_p] + [F] * 11 + [_I, _S]),
     "fv3_cubed_to_latlon": (C.c_int, [C.c_void_p, _I] + [F] * 8 + [_S]),
     "fv3_diag_pack": (C.c_int, [C.c_void_p, F, _I, _I, _I, _I, C.c_void_p, C.c_long, _S]),
     "fv3_diag_column_integral": (C.c_int, [C.c_void_p, F, F, C.c_void_p, C.c_long, _S]),

@@ -19,6 +19,10 @@ What does and does not interchange with the reference (stated, not assumed):
   ``h5netcdf`` or ``xarray`` in the environment (tried in that order); with none of them -- this image -- ``load_state`` says so
   instead of failing inside scipy.  Classic files (this build's own, or a reference file written with ``format="NETCDF3_64BIT"``)
   are read with scipy.
+* ``pt``: the files of the default mode hold the acoustic loop's ``T_v / pkz`` under that name.  A run that steps through
+  ``DynamicalCore`` (the driver's ``--temperature``) holds the temperature in K, as the reference does, and marks its files with
+  the global attribute ``pt_form = "temperature"`` (``save_state(..., pt_form=...)``); ``check_pt_form`` refuses the file of the
+  other mode.
 * ``load_state`` is strict: a requested variable that is missing from a file is an error (``allow_missing=True`` keeps what the
   state holds for it), so a restart can never silently continue from synthetic data.
 """
@@ -41,9 +45,15 @@ def _path(restart_path: str, rank: int) -> str:
     return os.path.join(restart_path, f"{PREFIX}_{rank}.nc")
 
 
-def save_state(state: DycoreState, local_ranks: Sequence[int], restart_path: str = "RESTART", names: Optional[Iterable[str]] = None, extra=None) -> list:
+PT_TEMPERATURE = "temperature"
+
+
+def save_state(state: DycoreState, local_ranks: Sequence[int], restart_path: str = "RESTART", names: Optional[Iterable[str]] = None, extra=None,
+               pt_form: Optional[str] = None) -> list:
     """Write one file per local rank; returns the paths.  ``local_ranks[i]`` is the global rank of sub-domain i.
-    ``extra``: {name: Quantity} written beside the state's fields (the tracers)."""
+    ``extra``: {name: Quantity} written beside the state's fields (the tracers).  ``pt_form``: what ``pt`` holds, written as the
+    global attribute ``pt_form`` -- ``"temperature"`` (K, the reference's contract: a state stepped through ``DynamicalCore``) or
+    None: no attribute, ``pt`` is the acoustic loop's ``T_v / pkz`` (the files of the default mode, unchanged)."""
     from scipy.io import netcdf_file
 
     os.makedirs(restart_path, exist_ok=True)
@@ -55,6 +65,8 @@ def save_state(state: DycoreState, local_ranks: Sequence[int], restart_path: str
         with netcdf_file(p, "w", version=2) as f:
             f.history = "pace_amd.restart.save_state"
             f.rank = np.int32(rank)
+            if pt_form is not None:
+                f.pt_form = str(pt_form)
             for n, q in fields:
                 a = q.numpy(i)  # (i, j[, k]) host copy of the full storage
                 dims = []
@@ -69,6 +81,32 @@ def save_state(state: DycoreState, local_ranks: Sequence[int], restart_path: str
                 v.dims = " ".join(q.dims)
         out.append(p)
     return out
+
+
+def pt_form(restart_path: str, rank: int) -> Optional[str]:
+    """The ``pt_form`` global attribute of one rank's restart file (None: the file has none -- ``pt`` is the loop's form)."""
+    p = _path(restart_path, rank)
+    if not os.path.exists(p):
+        raise FileNotFoundError(f"{p}: no restart file for rank {rank}")
+    with open(p, "rb") as fh:
+        magic = fh.read(4)
+    if magic[:3] != b"CDF":  # (a reference file: its pt is a temperature, but it carries no such attribute -- and no pkz of the loop)
+        return None
+    from scipy.io import netcdf_file
+
+    with netcdf_file(p, "r", mmap=False) as f:
+        v = getattr(f, "pt_form", None)
+    return v.decode() if isinstance(v, bytes) else (None if v is None else str(v))
+
+
+def check_pt_form(local_ranks: Sequence[int], restart_path: str, temperature: bool) -> None:
+    """Refuse restart files whose ``pt`` is not what the run steps: one sentence, as a ``ValueError``."""
+    for rank in local_ranks:
+        form = pt_form(restart_path, rank)
+        if temperature and form != PT_TEMPERATURE:
+            raise ValueError(f"{_path(restart_path, rank)} has no pt_form = \"temperature\" attribute: its pt is the acoustic loop's T_v / pkz, and a --temperature run restarts only from files written by one.")
+        if not temperature and form is not None:
+            raise ValueError(f"{_path(restart_path, rank)} has pt_form = \"{form}\": its pt is a temperature in K, and a run without --temperature restarts only from files written without it.")
 
 
 class MissingValuesError(RuntimeError):

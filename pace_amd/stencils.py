@@ -305,6 +305,37 @@ class LagrangianToEulerian(_Op):
             self._fillz(delp, tracers)  # delp is the Eulerian layer thickness by now: the reference's dp2
 
 
+class TemperatureToPotential(_Op):
+    """The preamble of ``fv_dynamics`` (``fv3_pt_from_temperature`` in include/fv3_mi355x.h holds the formulas): ``pt`` goes from
+    the temperature (K) the model state holds between steps to the form the acoustic loop transports, ``T_v / pkz``, and
+    ``pkz`` is rebuilt from the full (non-hydrostatic) pressure.  In place on the compute cells; ``delp``, ``delz``, ``q_con``,
+    ``cappa`` and ``qvapor`` (the specific humidity, None: a dry conversion) are only read."""
+
+    def __call__(self, pt, pkz, delp, delz, q_con, cappa, qvapor=None):
+        from . import lib as _lib
+
+        sf = self.sf
+        st = sf.lib.fv3_pt_from_temperature(sf.ctx, pt.fref, pkz.fref, delp.fref, delz.fref, q_con.fref, cappa.fref, _ref(qvapor), sf.stream_handle)
+        if st != 0:
+            raise _lib.Fv3Error(f"fv3_pt_from_temperature failed ({st}): " + sf.lib.fv3_last_error(sf.ctx).decode())
+
+
+class PotentialToTemperature(_Op):
+    """The last-step conversion of the remap (``fv3_temperature_from_pt``): ``pt`` goes from the loop's form back to the
+    temperature (K); ``omga`` (where given) becomes ``delp / delz * w`` and the 2-D ``ps`` (where given) the surface pressure
+    ``pe[.., nz]``.  ``recompute_pkz=False`` is FV3's own form ``T_v = pt * pkz``, valid right after a remap; ``True`` derives
+    ``T_v`` from the state alone and rebuilds ``pkz`` (a state whose ``pkz`` may be stale, e.g. one that was just initialised)."""
+
+    def __call__(self, pt, pkz, delp, delz, q_con, cappa, w, pe, qvapor=None, omga=None, ps=None, recompute_pkz=False):
+        from . import lib as _lib
+
+        sf = self.sf
+        st = sf.lib.fv3_temperature_from_pt(sf.ctx, pt.fref, pkz.fref, delp.fref, delz.fref, q_con.fref, cappa.fref, _ref(qvapor), w.fref, _ref(omga), pe.fref, _ref(ps),
+                                            1 if recompute_pkz else 0, sf.stream_handle)
+        if st != 0:
+            raise _lib.Fv3Error(f"fv3_temperature_from_pt failed ({st}): " + sf.lib.fv3_last_error(sf.ctx).decode())
+
+
 class CubedToLatLon(_Op):
     """``CubedToLatLon`` (FV3 ``fv_grid_utils.F90``: ``c2l_ord4`` / ``c2l_ord2``), the last operator of ``fv_dynamics``: the D-grid
     winds ``u``, ``v`` become the cell-centre winds ``ua`` (eastward) and ``va`` (northward) on the compute cells.  ``order``
