@@ -385,8 +385,8 @@ int fv3_fillz(fv3_ctx *, int n_tracers, const fv3_field *const *tracers, const f
  * 0 .. nz-1 of every sub-domain, in the build's Real, every product and quotient rounded on its own, left to right; halo cells,
  * the pad level nz and the fields that are only read are never written.  exp / log are the calls of fv3_remap's kernels.
  *   rrg = (Real)(-rdgas / grav), zvir = (Real)(rvgas / rdgas - 1), fac = (1 + zq) * (1 - q_con) with zq = zvir * qvapor, or
- *   zq = 0 where qvapor is NULL (bitwise what a qvapor field of zeros gives).  q_con and cappa are fields: what derives them
- *   (moist_cv) is outside this library.
+ *   zq = 0 where qvapor is NULL (bitwise what a qvapor field of zeros gives).  q_con and cappa are fields here: fv3_moist_cv
+ *   (below) derives them from the water species.
  *
  * fv3_pt_from_temperature, the preamble of fv_dynamics (pt: T in, the loop's form out; pkz: out):
  *   tv = pt * fac;  pz = exp(cappa * log(rrg * delp / delz * tv));  pkz = pz;  pt = tv / pz
@@ -405,6 +405,49 @@ int fv3_pt_from_temperature(fv3_ctx *, const fv3_field *pt, const fv3_field *pkz
 int fv3_temperature_from_pt(fv3_ctx *, const fv3_field *pt, const fv3_field *pkz, const fv3_field *delp, const fv3_field *delz,
                             const fv3_field *q_con, const fv3_field *cappa, const fv3_field *qvapor, const fv3_field *w,
                             const fv3_field *omga, const fv3_field *pe, const fv3_field *ps, int recompute_pkz, void *stream);
+
+/* ---- moist thermodynamics: q_con and cappa from the water species (fv3_moist.hip, fv3_remap.hip) --------------------------------
+ * FV3 derives the condensate mixing ratio q_con and the moist R / c_p (cappa) from the water species with moist_cv (fv_mapz.F90),
+ * once in the preamble of fv_dynamics and again inside every remap, after the tracers are remapped and filled and before pkz is
+ * rebuilt.  The nwat = 6 formula, in the build's Real, every sum, product and quotient rounded on its own in the order written:
+ *   qv = qvapor;  ql = qliquid + qrain;  qs = (qice + qsnow) + qgraupel
+ *   q_con = ql + qs
+ *   cvm   = (((1 - (qv + q_con)) * cv_air + qv * cv_vap) + ql * c_liq) + qs * c_ice
+ *   cappa = rdgas / (rdgas + cvm / (1 + zvir * qv))
+ * cv_air = (Real)(cp_air - rdgas), zvir = (Real)(rvgas / rdgas - 1), rdgas = (Real)rdgas from the context's constants; cv_vap, c_liq
+ * and c_ice (J/kg/K) travel with the species.  A species given as NULL is a field of zeros, bitwise; qvapor may not be NULL. */
+typedef struct {
+  const fv3_field *qvapor, *qliquid, *qrain, *qice, *qsnow, *qgraupel;
+  double cv_vap, c_liq, c_ice;
+} fv3_water;
+
+/* fv3_moist_cv: q_con, cappa and (where cvm is not NULL) cvm on the compute cells 1..nx x 1..ny, levels 0 .. nz-1 of every
+ * sub-domain; halo cells, the pad level and the species are never written.
+ *
+ * fv3_pt_from_temperature_moist: the preamble of fv_dynamics with moist_cv inside the cell.  q_con and cappa (both out) are formed
+ * from the species, then the formulas of fv3_pt_from_temperature with qvapor = water->qvapor (pt: T in, the loop's form out; pkz:
+ * out).  Bit for bit fv3_moist_cv followed by fv3_pt_from_temperature.
+ *
+ * FV3_ERR_ARG (a message that names the field, nothing launched, no field changed): a null context, a null fv3_water, a null
+ * qvapor, a null or wrongly shaped field or species, an output given twice, an output that is also a field that is only read. */
+int fv3_moist_cv(fv3_ctx *, const fv3_water *water, const fv3_field *q_con, const fv3_field *cappa, const fv3_field *cvm,
+                 void *stream);
+int fv3_pt_from_temperature_moist(fv3_ctx *, const fv3_field *pt, const fv3_field *pkz, const fv3_field *delp,
+                                  const fv3_field *delz, const fv3_field *q_con, const fv3_field *cappa, const fv3_water *water,
+                                  void *stream);
+
+/* fv3_remap_moist: fv3_remap with moist_cv where FV3 has it.  The T_v kernel at the top reads the incoming cappa; the fields are
+ * remapped as by fv3_remap; with fill != 0 the negative means of all tracers are then filled in the vertical with the Eulerian
+ * layer thickness (bitwise fv3_fillz on the final delp); the closing column kernel forms q_con and cappa per level from the remapped
+ * and filled species, stores them (q_con: out; cappa: in, then out) and uses the new cappa for
+ * pkz = exp(cappa * log(rrg * delp / delz * tv)), pt = tv / pkz.  The species are the fields that get remapped: each one given must
+ * be one of `tracers` (the same storage).  Everything but q_con, cappa, pkz and pt is bitwise what fv3_remap (+ fv3_fillz) gives.
+ * FV3_ERR_ARG (a message, nothing launched, no field changed): what fv3_remap and fv3_moist_cv reject, a species that is not among
+ * the tracers, a tracer given twice, q_con given as another argument.  FV3_ERR_UNSUPPORTED: nz < 5. */
+int fv3_remap_moist(fv3_ctx *, int n_tracers, const fv3_field *const *tracers, const fv3_field *pt, const fv3_field *delp,
+                    const fv3_field *delz, const fv3_field *peln, const fv3_field *pe, const fv3_field *pk, const fv3_field *pkz,
+                    const fv3_field *u, const fv3_field *v, const fv3_field *w, const fv3_field *cappa, const fv3_field *q_con,
+                    const fv3_field *ps, const fv3_field *wsd, const fv3_water *water, int fill, void *stream);
 
 /* CubedToLatLon (the last operator of fv_dynamics: FV3 fv_grid_utils.F90 c2l_ord4 / c2l_ord2; pyFV3 CubedToLatLon, savepoint
  * FVDynamics-Out ua / va [REF tests/savepoint/thresholds/fv_dynamics.yaml]).  D-grid u, v -> ua, va on the compute cells in earth

@@ -86,6 +86,13 @@ GEOS = ConstantSet(
     DZ_MIN=6.0,
 )
 
+# Heat capacities of the water species in moist_cv (J/kg/K), restated from FV3's fv_mapz.F90: cv_vap = 3 rvgas, c_liq, c_ice.  They are
+# run-time data of the moist entries (``fv3_water`` in include/fv3_mi355x.h), not part of ``fv3_constants``.  Newer FV3 branches carry
+# c_liq = 4218, c_ice = 2106 ("Uncertain restatements").
+CV_VAP = 3.0 * 461.50
+C_LIQ = 4185.5
+C_ICE = 1972.0
+
 _SETS = {"GFS": GFS, "GFDL": GFDL, "GEOS": GEOS}
 
 

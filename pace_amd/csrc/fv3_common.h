@@ -346,6 +346,7 @@ bool fv3_pp_ensure(fv3_ctx *c);  // (fv3_ctx.hip) the ping-pong buffers of fv3_a
 bool fv3_acc_slots_ensure(fv3_ctx *c, int n_sub_steps);  // (fv3_ctx.hip) the per-sub-step flux arrays of the deferred accumulation
 void fv3_h2d(void *dst, const void *src, size_t bytes);
 int fv3_post(fv3_ctx *c, fv3_stream_t s, const char *what);
+void fv3_fillz_launch(fv3_ctx *c, fv3_stream_t s, int n_tracers, Real *const *q, const Real *dp);  // fv3_fillz.hip
 // validate one field against the context layout; returns typed base pointer or nullptr
 Real *fv3_chk(fv3_ctx *c, const fv3_field *f, const char *name, bool is2d = false);
 

@@ -150,6 +150,21 @@ void fillz_launch(fv3_ctx *c, fv3_stream_t s, Real *const *q, const Real *dp) {
 
 }  // namespace
 
+// the launches of fv3_fillz on checked pointers (n_tracers >= 1, nz >= 2, no field given twice): also the filling step of fv3_remap_moist
+void fv3_fillz_launch(fv3_ctx *c, fv3_stream_t s, int n_tracers, Real *const *q, const Real *dp) {
+  for (int n0 = 0; n0 < n_tracers; n0 += FZ_MAXG) {
+    const int ng = n_tracers - n0 < FZ_MAXG ? n_tracers - n0 : FZ_MAXG;
+    if (ng == 4)
+      fillz_launch<4>(c, s, q + n0, dp);
+    else if (ng == 3)
+      fillz_launch<3>(c, s, q + n0, dp);
+    else if (ng == 2)
+      fillz_launch<2>(c, s, q + n0, dp);
+    else
+      fillz_launch<1>(c, s, q + n0, dp);
+  }
+}
+
 extern "C" int fv3_fillz(fv3_ctx *c, int n_tracers, const fv3_field *const *tracers, const fv3_field *dp_, void *stream) {
   if (!c) return FV3_ERR_ARG;
   if (n_tracers < 0) return fv3_fail(c, FV3_ERR_ARG, "fillz: n_tracers = " + std::to_string(n_tracers) + " is negative");
@@ -167,16 +182,6 @@ extern "C" int fv3_fillz(fv3_ctx *c, int n_tracers, const fv3_field *const *trac
   if (c->g.nz < 2) return fv3_fail(c, FV3_ERR_UNSUPPORTED, "fillz: needs at least 2 levels (nz = " + std::to_string(c->g.nz) + ")");
   if (n_tracers == 0) return FV3_OK;
   fv3_stream_t s = (fv3_stream_t)stream;
-  for (int n0 = 0; n0 < n_tracers; n0 += FZ_MAXG) {
-    const int ng = n_tracers - n0 < FZ_MAXG ? n_tracers - n0 : FZ_MAXG;
-    if (ng == 4)
-      fillz_launch<4>(c, s, q.data() + n0, dp);
-    else if (ng == 3)
-      fillz_launch<3>(c, s, q.data() + n0, dp);
-    else if (ng == 2)
-      fillz_launch<2>(c, s, q.data() + n0, dp);
-    else
-      fillz_launch<1>(c, s, q.data() + n0, dp);
-  }
+  fv3_fillz_launch(c, s, n_tracers, q.data(), dp);
   return fv3_post(c, s, "fillz");
 }

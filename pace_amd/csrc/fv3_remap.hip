@@ -7,12 +7,17 @@
 // adjustment, omga untouched.  The vertical filling of negative tracer means (`fill: true`) is fv3_fillz (fv3_fillz.hip), called
 // right after this entry with the remapped tracers and delp.
 //
+// fv3_remap_moist is the same remap with FV3's moist_cv where FV3 has it: remap, fill (here: inside the entry, with the Eulerian
+// thickness), q_con and cappa from the remapped and filled species, then pkz with the new cappa.  One body (remap_all) serves both
+// entries; the closing column kernel is templated on "moist".
+//
 // A thread owns a column (i fastest: every level access of a wave is one coalesced row).  What a column needs beyond
 // O(1) registers are the edge values of the parabolas (a tridiagonal solve in k): two scratch fields (the elimination factors
 // and the edge values); the limited parabola of a source layer is a function of the edge values and five neighbouring means
 // only, so it is rebuilt where the conservative integration needs it instead of being stored (the Fortran keeps a4(4, km)
 // per column).  The Lagrangian interface pressures are the pe / peln fields the last acoustic sub-step left (riem_solver3
 // with last_call, edge_pe for the ring the D-grid winds average over); the Eulerian ones are ak + bk * ps on the fly.
+#include "fv3_moist.h"
 #include "fv3_ops.h"
 
 namespace {
@@ -296,23 +301,110 @@ FV3_HD inline void remap_col(int km, PE1 pe1, PE2 pe2, Q1F Q1, GAMF GAM, QEF QE,
   }
 }
 
-}  // namespace
 
 // The scratch accessors below index [level][column] fields: K(arr, k).
 #define RK(arr, k) ((arr) + tb + (long)(k)*g.sk)[pix]
 
-extern "C" int fv3_remap(fv3_ctx *c, int n_tracers, const fv3_field *const *tracers, const fv3_field *pt_, const fv3_field *delp_, const fv3_field *delz_,
-                         const fv3_field *peln_, const fv3_field *pe_, const fv3_field *pk_, const fv3_field *pkz_, const fv3_field *u_, const fv3_field *v_,
-                         const fv3_field *w_, const fv3_field *cappa_, const fv3_field *ps_, const fv3_field *wsd_, void *stream) {
+struct CloseArgs {
+  Real *pt, *delp, *delz, *peln, *pe, *pk, *pkz, *cappa, *ps;
+  const Real *TV, *ak, *bk;
+  Real *q_con;  // (the moist form only)
+  Real ptop, akap, rrg;
+};
+
+// The closing column kernel: Eulerian pressures, pkz from the remapped T_v, pt back to the loop's form, the new layer thickness.
+// MOIST: q_con and cappa of every level are formed from the remapped (and filled) species first (moist_cv, fv3_moist.h), stored, and
+// the new cappa is the one pkz is built with; otherwise cappa is the given field.
+template <bool MOIST>
+void remap_close(fv3_ctx *c, fv3_stream_t s, const CloseArgs a, const MoistIn m) {
+  const Geo g = c->g;
+  const int km = g.nz;
+  Real *const pt = a.pt, *const delp = a.delp, *const delz = a.delz, *const peln = a.peln, *const pe = a.pe, *const pk = a.pk, *const pkz = a.pkz, *const cappa = a.cappa;
+  Real *const ps = a.ps, *const q_con = a.q_con;
+  const Real *const TV = a.TV, *const ak = a.ak, *const bk = a.bk;
+  const Real ptop = a.ptop, akap = a.akap, rrg = a.rrg;
+  launch2(c, s, Box{1, g.nx, 1, g.ny, 0, 0}, [=] FV3_HD(int t, int i, int j) {
+    const long tb = t * g.st;
+    const unsigned pix = IX(i, j);
+    const Real psv = RK(pe, km);
+    ps[t * g.st2 + pix] = psv;
+    Real p0 = ptop;
+    RK(peln, 0) = log(ptop);
+    RK(pk, 0) = exp(akap * log(ptop));
+    for (int k = 0; k < km; ++k) {
+      const Real p1 = k + 1 == km ? psv : ak[k + 1] + bk[k + 1] * psv;
+      const Real dp2 = p1 - p0;
+      Real cp;
+      if constexpr (MOIST) {
+        const MoistCell o = moist_cell(m, tb + (long)k * g.sk + pix);
+        RK(q_con, k) = o.q_con;
+        RK(cappa, k) = o.cappa;
+        cp = o.cappa;
+      } else {
+        cp = RK(cappa, k);
+      }
+      const Real tv = RK(TV, k);
+      const Real pz = exp(cp * log(rrg * dp2 / RK(delz, k) * tv));
+      RK(pkz, k) = pz;
+      RK(pt, k) = tv / pz;
+      RK(delp, k) = dp2;
+      if (k + 1 < km) {
+        const Real pn = log(p1);
+        RK(pe, k + 1) = p1;
+        RK(peln, k + 1) = pn;
+        RK(pk, k + 1) = exp(akap * pn);
+      } else {
+        RK(pk, km) = exp(akap * RK(peln, km));
+      }
+      p0 = p1;
+    }
+    RK(pe, 0) = ptop;
+  });
+}
+
+// fv3_remap (water == nullptr: q_con_ and fill are not read) and fv3_remap_moist
+int remap_all(fv3_ctx *c, int n_tracers, const fv3_field *const *tracers, const fv3_field *pt_, const fv3_field *delp_, const fv3_field *delz_, const fv3_field *peln_,
+              const fv3_field *pe_, const fv3_field *pk_, const fv3_field *pkz_, const fv3_field *u_, const fv3_field *v_, const fv3_field *w_, const fv3_field *cappa_,
+              const fv3_field *q_con_, const fv3_field *ps_, const fv3_field *wsd_, const fv3_water *water, int fill, void *stream) {
+  if (water) {  // (fv3_remap_moist has checked the context)
+    if (n_tracers < 0) return fv3_fail(c, FV3_ERR_ARG, "remap_moist: n_tracers = " + std::to_string(n_tracers) + " is negative");
+    if (n_tracers > 0 && !tracers) return fv3_fail(c, FV3_ERR_ARG, "remap_moist: the tracer list is null with n_tracers = " + std::to_string(n_tracers));
+  }
   if (!c || n_tracers < 0 || (n_tracers && !tracers)) return FV3_ERR_ARG;
   FV3_FIELD(pt, pt_) FV3_FIELD(delp, delp_) FV3_FIELD(delz, delz_) FV3_FIELD(peln, peln_) FV3_FIELD(pe, pe_) FV3_FIELD(pk, pk_) FV3_FIELD(pkz, pkz_)
   FV3_FIELD(u, u_) FV3_FIELD(v, v_) FV3_FIELD(w, w_) FV3_FIELD(cappa, cappa_) FV3_FIELD2D(ps, ps_) FV3_FIELD2D(wsd, wsd_)
   const Geo g = c->g;
-  if (g.nz < 5) return fv3_fail(c, FV3_ERR_UNSUPPORTED, "remap: needs at least 5 levels (two monotone layers at either end + an interior)");
+  if (g.nz < 5) return fv3_fail(c, FV3_ERR_UNSUPPORTED, std::string(water ? "remap_moist" : "remap") + ": needs at least 5 levels (two monotone layers at either end + an interior)");
   std::vector<Real *> q(n_tracers);
   for (int n = 0; n < n_tracers; ++n) {
     q[n] = fv3_chk(c, tracers[n], "tracer");
     if (!q[n]) return FV3_ERR_ARG;
+  }
+  MoistIn m{};
+  Real *q_con = nullptr;
+  if (water) {
+    if (int st = fv3_moist_in(c, "remap_moist", water, &m)) return st;
+    q_con = fv3_chk(c, q_con_, "q_con_");
+    if (!q_con) return FV3_ERR_ARG;
+    // the species are what gets remapped and filled: each one is one of the tracers; a tracer given twice would be remapped twice
+    MoistNamed sp[6];
+    const int n_sp = fv3_moist_named(m, sp);
+    for (int a = 0; a < n_sp; ++a) {
+      bool found = false;
+      for (int n = 0; n < n_tracers; ++n) found = found || q[n] == sp[a].ptr;
+      if (!found) return fv3_fail(c, FV3_ERR_ARG, std::string("remap_moist: ") + sp[a].name + " is not among the tracers (the species are the fields that get remapped)");
+    }
+    for (int n = 0; n < n_tracers; ++n)
+      for (int l = 0; l < n; ++l)
+        if (q[l] == q[n]) return fv3_fail(c, FV3_ERR_ARG, "remap_moist: tracers " + std::to_string(l) + " and " + std::to_string(n) + " are the same field");
+    // q_con is written beside fields that are read and written by the same kernels: it may be none of them
+    const MoistNamed other[] = {{"pt", pt}, {"delp", delp}, {"delz", delz}, {"peln", peln}, {"pe", pe}, {"pk", pk}, {"pkz", pkz}, {"u", u}, {"v", v}, {"w", w}, {"cappa", cappa}};
+    for (const MoistNamed &o : other)
+      if (o.ptr == q_con) return fv3_fail(c, FV3_ERR_ARG, std::string("remap_moist: q_con is the ") + o.name + " field");
+    for (int n = 0; n < n_tracers; ++n) {
+      if (q[n] == q_con) return fv3_fail(c, FV3_ERR_ARG, "remap_moist: q_con is tracer " + std::to_string(n));
+      if (q[n] == cappa) return fv3_fail(c, FV3_ERR_ARG, "remap_moist: cappa is tracer " + std::to_string(n));
+    }
   }
   fv3_stream_t s = (fv3_stream_t)stream;
   const int km = g.nz;
@@ -386,34 +478,40 @@ extern "C" int fv3_remap(fv3_ctx *c, int n_tracers, const fv3_field *const *trac
   };
   wind(u, true);
   wind(v, false);
+  // ---- fill: true -- the negative tracer means are filled with the Eulerian thickness before moist_cv reads the condensate.  The
+  //      Lagrangian delp has been read for the last time (the delz kernel above): it becomes dp2 here, formed as the closing kernel
+  //      forms it, so the filling is fv3_fillz on the final delp
+  if (water && fill && n_tracers) {
+    launch3<4>(c, s, Box{1, g.nx, 1, g.ny, 0, km - 1}, [=] FV3_HD(int t, int k, int i, int j) {
+      const unsigned pix = IX(i, j);
+      const long tb = t * g.st;
+      const Real psv = RK(pe, km);
+      const Real p0 = k == 0 ? ptop : ak[k] + bk[k] * psv, p1 = k + 1 == km ? psv : ak[k + 1] + bk[k + 1] * psv;
+      RK(delp, k) = p1 - p0;
+    });
+    fv3_fillz_launch(c, s, n_tracers, q.data(), delp);
+  }
   // ---- Eulerian pressures, pkz from the remapped T_v, pt back to the loop's form, the new layer thickness
-  launch2(c, s, cells, [=] FV3_HD(int t, int i, int j) {
-    const long tb = t * g.st;
-    const unsigned pix = IX(i, j);
-    const Real psv = RK(pe, km);
-    ps[t * g.st2 + pix] = psv;
-    Real p0 = ptop;
-    RK(peln, 0) = log(ptop);
-    RK(pk, 0) = exp(akap * log(ptop));
-    for (int k = 0; k < km; ++k) {
-      const Real p1 = k + 1 == km ? psv : ak[k + 1] + bk[k + 1] * psv;
-      const Real dp2 = p1 - p0;
-      const Real cp = RK(cappa, k), tv = RK(TV, k);
-      const Real pz = exp(cp * log(rrg * dp2 / RK(delz, k) * tv));
-      RK(pkz, k) = pz;
-      RK(pt, k) = tv / pz;
-      RK(delp, k) = dp2;
-      if (k + 1 < km) {
-        const Real pn = log(p1);
-        RK(pe, k + 1) = p1;
-        RK(peln, k + 1) = pn;
-        RK(pk, k + 1) = exp(akap * pn);
-      } else {
-        RK(pk, km) = exp(akap * RK(peln, km));
-      }
-      p0 = p1;
-    }
-    RK(pe, 0) = ptop;
-  });
-  return fv3_post(c, s, "remap");
+  const CloseArgs ca{pt, delp, delz, peln, pe, pk, pkz, cappa, ps, TV, ak, bk, q_con, ptop, akap, rrg};
+  if (water)
+    remap_close<true>(c, s, ca, m);
+  else
+    remap_close<false>(c, s, ca, m);
+  return fv3_post(c, s, water ? "remap_moist" : "remap");
+}
+
+}  // namespace
+
+extern "C" int fv3_remap(fv3_ctx *c, int n_tracers, const fv3_field *const *tracers, const fv3_field *pt, const fv3_field *delp, const fv3_field *delz, const fv3_field *peln,
+                         const fv3_field *pe, const fv3_field *pk, const fv3_field *pkz, const fv3_field *u, const fv3_field *v, const fv3_field *w, const fv3_field *cappa,
+                         const fv3_field *ps, const fv3_field *wsd, void *stream) {
+  return remap_all(c, n_tracers, tracers, pt, delp, delz, peln, pe, pk, pkz, u, v, w, cappa, nullptr, ps, wsd, nullptr, 0, stream);
+}
+
+extern "C" int fv3_remap_moist(fv3_ctx *c, int n_tracers, const fv3_field *const *tracers, const fv3_field *pt, const fv3_field *delp, const fv3_field *delz,
+                               const fv3_field *peln, const fv3_field *pe, const fv3_field *pk, const fv3_field *pkz, const fv3_field *u, const fv3_field *v, const fv3_field *w,
+                               const fv3_field *cappa, const fv3_field *q_con, const fv3_field *ps, const fv3_field *wsd, const fv3_water *water, int fill, void *stream) {
+  if (!c) return fv3_fail(c, FV3_ERR_ARG, "remap_moist: the context is null");
+  if (!water) return fv3_fail(c, FV3_ERR_ARG, "remap_moist: the fv3_water is null");
+  return remap_all(c, n_tracers, tracers, pt, delp, delz, peln, pe, pk, pkz, u, v, w, cappa, q_con, ps, wsd, water, fill, stream);
 }

@@ -7,7 +7,9 @@ It reproduces the reference's time loop for ``dycore_only: true`` + ``disable_st
 [AcousticDynamics (+ tracer advection with ``--tracers N``, + the vertical remap with ``--remap``, +
 the vertical filling of negative tracer values at the end of the remap with ``dycore_config.fill: true`` or ``--fill on``)] -- with
 ``--temperature`` (needs ``--remap``) the step is ``DynamicalCore.step_dynamics``: ``pt`` is a temperature in K before and after it,
-``omga`` and ``ps`` are diagnosed, and the start-up line and the json ``setup`` say ``"pt": "temperature"`` (otherwise ``"loop"``) -- and writes
+``omga`` and ``ps`` are diagnosed, and the start-up line and the json ``setup`` say ``"pt": "temperature"`` (otherwise ``"loop"``); with ``--moist``
+(needs ``--temperature --remap`` and ``nwat: 6``) the first six tracers are the water species, ``q_con`` and ``cappa`` follow them through
+``moist_cv`` and the start-up line and the json say ``"thermodynamics": "moist_cv"`` (otherwise ``"given"``) -- and writes
 the per-step times in the layout the reference's performance collector uses
 (``{"times": {<timer>: {"hits": n, "times": [[...per step...] per rank]}}}``, timers ``mainloop``, ``DynCore``,
 ``TracerAdvection``, ``Remapping`` [REF tests/main/driver/test_driver.py:77-121]).  With ``--tracers N --remap`` the step is the
@@ -28,7 +30,7 @@ Diagnostics [REF driver/pace/driver/driver.py:551-552, 588-611, 702-705]: with a
 (``pace_amd.diagnostics.DiagnosticsConfig``) the driver stores the initial state when ``output_initial_state`` is set, stores after
 every ``output_frequency``-th step -- outside the step clock -- and ends with ``store_grid`` and ``cleanup``.  Names of the block that
 this build's state does not hold (``qvapor`` ... ``qgraupel``, ``ps``: the reference's yamls ask for them) are dropped and reported in
-one line; with ``--temperature`` ``ps`` is known and stored from ``DynamicalCore.ps``.  ``--diagnostics-path DIR`` overrides the block's ``path``, ``--no-diagnostics`` turns the block off.  Without a block
+one line; with ``--moist`` the six species are tracers of the step and are stored; with ``--temperature`` ``ps`` is known and stored from ``DynamicalCore.ps``.  ``--diagnostics-path DIR`` overrides the block's ``path``, ``--no-diagnostics`` turns the block off.  Without a block
 nothing changes.
 """
 from __future__ import annotations
@@ -55,6 +57,7 @@ def load_config(path: str):
         total += float(y.get(key, 0) or 0) * mult
     dt_atmos = float(y["dt_atmos"])
     run = dict(
+        nwat=(y.get("dycore_config") or {}).get("nwat", None),
         nx_tile=int(y["nx_tile"]),
         nz=int(y["nz"]),
         layout=tuple(int(v) for v in y.get("layout", (1, 1))),
@@ -132,12 +135,22 @@ def main(argv=None):
                     help="CubedToLatLon at the end of every step (c2l_ord from the yaml, default 4): state ua / va become the eastward / northward cell-centre winds")
     ap.add_argument("--temperature", action="store_true",
                     help="step through DynamicalCore.step_dynamics (needs --remap): state pt is a temperature in K before and after every step, omga = delp / delz * w and ps are diagnosed")
+    ap.add_argument("--moist", action="store_true",
+                    help="derive q_con and cappa from six water species with moist_cv in the preamble and in every remap (needs --temperature --remap and nwat: 6 in the yaml; "
+                         "the first six tracers are qvapor, qliquid, qice, qrain, qsnow, qgraupel and --tracers is raised to at least 6)")
     ap.add_argument("--diagnostics-path", default=None, help="directory of the diagnostics (overrides diagnostics_config.path of the yaml)")
     ap.add_argument("--no-diagnostics", action="store_true", help="ignore the yaml's diagnostics_config block")
     a = ap.parse_args(argv)
     if a.temperature and not a.remap:
         sys.exit("--temperature needs --remap: the conversion back to temperature is the last step of the remap")
+    if a.moist and not (a.temperature and a.remap):
+        sys.exit("--moist needs --temperature --remap: moist_cv sits in the preamble and the remap of DynamicalCore.step_dynamics")
     run, dy, ignored = load_config(a.config)
+    if a.moist:
+        if run["nwat"] is None or int(run["nwat"]) != 6:
+            sys.exit(f"--moist needs dycore_config.nwat: 6 in the yaml (it has nwat: {run['nwat']}): moist_cv is built for the six-species formula only")
+        a.tracers = max(a.tracers, 6)
+        ignored = [k for k in ignored if k != "nwat"]  # (read above; without --moist it stays in the list of keys not read)
 
     import torch
 
@@ -158,6 +171,9 @@ def main(argv=None):
     say(f'"fill": {str(fill).lower()}' + ("" if a.fill == "yaml" else f" (--fill {a.fill})")
         + ("  (ignored without --tracers N --remap)" if (not fill and (a.fill == "on" or (a.fill == "yaml" and dy.get("fill")))) else ""))
     say(f'"pt": "{pt_form}"' + ("  (DynamicalCore.step_dynamics: temperature in K in and out, omga and ps diagnosed)" if a.temperature else "  (the acoustic loop's T_v / pkz; --temperature --remap: temperature in K)"))
+    thermo = "moist_cv" if a.moist else "given"
+    say(f'"thermodynamics": "{thermo}"' + ("  (q_con and cappa from qvapor, qliquid, qice, qrain, qsnow, qgraupel in the preamble and in every remap)" if a.moist
+                                         else "  (q_con and cappa are the state's fields as initialised; --moist --temperature --remap: moist_cv of six water species)"))
     if run["init"] == "analytic" and str(run["case"]).startswith("baroclinic"):
         init = "baroclinic"
         say("initialization: JW2006 baroclinic wave (pace_amd.init.baroclinic_state; restated from the paper, see its docstring)")
@@ -179,7 +195,7 @@ def main(argv=None):
     kw = {k: dy[k] for k in ("k_split", "n_split") if k in dy}
     h = DycoreHarness(nx_tile=run["nx_tile"], nz=run["nz"], layout=run["layout"], dt_atmos=run["dt_atmos"], world_size=world, proc=rank,
                       device=f"cuda:{local_rank}", dtype=dtype, verbose=(rank == 0), init=init, config_overrides={k: v for k, v in dy.items() if k not in ("k_split", "n_split", "fill")},
-                      n_tracers=a.tracers, hord_tr=int(dy.get("hord_tr", 8)), remap=a.remap, fill=fill, latlon_winds=a.latlon_winds, temperature=a.temperature, **kw)
+                      n_tracers=a.tracers, hord_tr=int(dy.get("hord_tr", 8)), remap=a.remap, fill=fill, latlon_winds=a.latlon_winds, temperature=a.temperature, moist=a.moist, **kw)
     if run["device_sync"]:
         h.sf.set_device_sync(True)
     if a.restart:
@@ -266,18 +282,20 @@ def main(argv=None):
         sdpd = run["dt_atmos"] / mean
         out = a.out or f"{run['experiment']}_fv3_mi355x.json"
         json.dump({"setup": {"experiment": run["experiment"], "nx_tile": run["nx_tile"], "nz": run["nz"], "layout": list(run["layout"]), "dt_atmos": run["dt_atmos"],
-                             "k_split": h.cfg.k_split, "n_split": h.cfg.n_split, "n_gpus": world, "backend": "hip:gfx950", "dycore_only": True, "acoustic_only": not (a.tracers or a.remap), "tracers": a.tracers, "remap": bool(a.remap), "fill": fill, "pt": pt_form, "finite": ok,
+                             "k_split": h.cfg.k_split, "n_split": h.cfg.n_split, "n_gpus": world, "backend": "hip:gfx950", "dycore_only": True, "acoustic_only": not (a.tracers or a.remap), "tracers": a.tracers, "remap": bool(a.remap), "fill": fill, "pt": pt_form, "thermodynamics": thermo, "finite": ok,
                              "note": ("a step here is k_split AcousticDynamics calls; the reference's dycore_only mainloop (DynamicalCore.step_dynamics) also runs tracer "
                                       "advection and the Lagrangian-to-Eulerian remap (--tracers N --remap add them): not comparable with the reference's 'mainloop' timer")
                              if not (a.tracers and a.remap) else
                              "a step is k_split x [AcousticDynamics, tracer advection, vertical remap] = the body of DynamicalCore.step_dynamics without physics and "
-                             "moist thermodynamics"},
+                             + ("the saturation adjustment (q_con and cappa follow the six water species: moist_cv)" if a.moist else "moist thermodynamics")},
                    # the reference collector's layout: times.<timer> = {hits, times[rank][step]}; "mainloop" only when the step is the
                    # whole body of step_dynamics (--tracers N --remap), then .jenkins/print_performance_number.py runs on this file as is
                    "times": report,
                    "times_note": ("only the outer clock ('" + loop_name + "') synchronises the device; the nested clocks (DynCore / TracerAdvection / Remapping) are host-side "
-                                  "enqueue intervals. " + ("'mainloop' here = the dry body of step_dynamics with N synthetic tracers: no moist thermodynamics, no physics coupling "
-                                                           "-- the reference's mainloop does more per step." if full_step else "")),
+                                  "enqueue intervals. " + (("'mainloop' here = the body of step_dynamics with moist_cv of six water species: no saturation adjustment, no physics coupling "
+                                                            "-- the reference's mainloop does more per step." if a.moist else
+                                                            "'mainloop' here = the dry body of step_dynamics with N synthetic tracers: no moist thermodynamics, no physics coupling "
+                                                            "-- the reference's mainloop does more per step.") if full_step else "")),
                    ("acoustic_simulated_days_per_day" if not (a.tracers or a.remap) else "dynamics_simulated_days_per_day"): sdpd}, open(out, "w"))
         say(f"{n_steps} steps of dt_atmos={run['dt_atmos']:g}s: acoustic mainloop mean (first step dropped) {mean * 1e3:.2f} ms -> {sdpd:.2f} simulated-days/day ({'acoustic dynamics only' if not (a.tracers or a.remap) else 'acoustic dynamics' + (f' + {a.tracers} tracers' if a.tracers else '') + (' + remap' if a.remap else '')}); state finite: {ok}; wrote {out}")
     return 0

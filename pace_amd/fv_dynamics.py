@@ -12,8 +12,12 @@ The contract of the call is the reference's: ``state.pt`` holds the temperature 
    ``state.omga = delp / delz * w`` and the surface pressure ``DynamicalCore.ps``,
 4. :class:`~pace_amd.stencils.CubedToLatLon`, where asked ("CubedToLatLon").
 
-``q_con`` and ``cappa`` are fields of the state: what derives them from the water species (``moist_cv``) is outside this build, as
-are the saturation adjustment and the physics coupling.  Every buffer (``dp1``, ``ps``, the operators' own) is allocated by the
+Without ``water_species`` ``q_con`` and ``cappa`` are fields of the state that the caller provides.  With it they are derived from
+the six water species by FV3's ``moist_cv`` where FV3 derives them: step 1 becomes the moist preamble
+(``fv3_pt_from_temperature_moist``: ``q_con``, ``cappa`` from the species, then the conversion) and the remap of step 2 the moist remap
+(``fv3_remap_moist``: remap, fill, ``q_con`` / ``cappa`` from the remapped and filled species, ``pkz`` with the new ``cappa``); step 3 is
+unchanged and reads the ``q_con`` the last remap wrote.  The saturation adjustment, the energy fixer and the physics coupling are
+outside this build.  Every buffer (``dp1``, ``ps``, the operators' own) is allocated by the
 constructor; ``step_dynamics`` allocates nothing.
 """
 from __future__ import annotations
@@ -44,12 +48,16 @@ class DynamicalCore:
         hord_tr: int = 8,
         vapor: Optional[str] = None,
         cubed_to_latlon: bool = True,
+        water_species: Optional[Dict[str, str]] = None,
     ):
         """Arguments as the reference's call.  ``comm``: a :class:`pace_amd.halo.Layout` (None: every rank in this process);
         ``timestep``: the model step ``dt_atmos`` in seconds or as a ``timedelta`` (None: ``config.dt_atmos``); ``tracers``:
         ``{name: Quantity}`` advected and remapped with the step (may be empty); ``vapor``: the name of the tracer that is the
         specific humidity (None: a dry conversion between temperature and virtual temperature); ``hord_tr``: the tracers'
-        transport scheme; ``cubed_to_latlon``: end the step with the eastward / northward ``ua``, ``va``."""
+        transport scheme; ``cubed_to_latlon``: end the step with the eastward / northward ``ua``, ``va``; ``water_species``:
+        ``{role: tracer name}`` for the roles ``qvapor``, ``qliquid``, ``qrain``, ``qice``, ``qsnow``, ``qgraupel`` (a missing role is a
+        field of zeros; ``qvapor`` is required and becomes ``vapor``) -- ``q_con`` and ``cappa`` are then derived from these tracers
+        (``moist_cv``) in the preamble and in every remap; None: they are the state's fields as the caller left them."""
         sf = stencil_factory
         qf = quantity_factory or sf.quantity_factory
         self.sf, self.qf = sf, qf
@@ -58,6 +66,12 @@ class DynamicalCore:
             timestep = self.config.dt_atmos
         self.timestep = float(timestep.total_seconds()) if hasattr(timestep, "total_seconds") else float(timestep)
         self.tracers = dict(tracers or {})
+        self.water = None
+        if water_species is not None:
+            self.water = st.WaterSpecies.from_tracers(self.tracers, dict(water_species))
+            if vapor is not None and vapor != water_species["qvapor"]:
+                raise ValueError(f"vapor={vapor!r} differs from water_species['qvapor']={water_species['qvapor']!r}")
+            vapor = water_species["qvapor"]
         if vapor is not None and vapor not in self.tracers:
             raise ValueError(f"vapor={vapor!r} is not among the tracers ({', '.join(self.tracers) or 'none'})")
         self.vapor = vapor
@@ -89,7 +103,8 @@ class DynamicalCore:
 
         timer = timer or NullTimer()
         s, dyn, tracers, qv = state, self.acoustic_dynamics, self.tracers, self.qvapor
-        self.temperature_to_potential(s.pt, s.pkz, s.delp, s.delz, s.q_con, s.cappa, qv)
+        water = self.water
+        self.temperature_to_potential(s.pt, s.pkz, s.delp, s.delz, s.q_con, s.cappa, qv, water=water)
         k_split = self.config.k_split
         dt = self.timestep / k_split
         for k in range(k_split):
@@ -102,7 +117,7 @@ class DynamicalCore:
                     self._tracer_halo.update()
                     self.tracer_advection(tracers, self.dp1, s.mfxd, s.mfyd, s.cxd, s.cyd)
             with timer.clock("Remapping"):
-                self.remap(tracers, s.pt, s.delp, s.delz, s.peln, s.pe, s.pk, s.pkz, s.u, s.v, s.w, s.cappa, self.ps, dyn._wsd)
+                self.remap(tracers, s.pt, s.delp, s.delz, s.peln, s.pe, s.pk, s.pkz, s.u, s.v, s.w, s.cappa, self.ps, dyn._wsd, q_con=s.q_con, water=water)
         # the last-step conversion of the remap: pkz is the one the remap has just formed with these delp, delz and T_v
         self.potential_to_temperature(s.pt, s.pkz, s.delp, s.delz, s.q_con, s.cappa, s.w, s.pe, qvapor=qv, omga=s.omga, ps=self.ps, recompute_pkz=False)
         if self.cubed_to_latlon is not None:

@@ -9,7 +9,8 @@ together the body of ``DynamicalCore.step_dynamics``; no physics, no moist therm
 tracer values at the end of the remap (the namelist's ``fill``); ``latlon_winds`` the CubedToLatLon that
 ends ``fv_dynamics`` (eastward / northward ``ua``, ``va``); ``temperature`` (needs ``remap``) makes the step
 ``DynamicalCore.step_dynamics`` (pace_amd/fv_dynamics.py): ``state.pt`` is then a temperature in K between steps, ``omga`` and ``ps`` are
-diagnosed, ``vapor`` names the tracer that is the specific humidity.
+diagnosed, ``vapor`` names the tracer that is the specific humidity; ``moist`` (needs ``temperature``) names the first six tracers
+after the water species and lets ``q_con`` / ``cappa`` follow them (``moist_cv`` in the preamble and in every remap).
 """
 from __future__ import annotations
 
@@ -39,6 +40,11 @@ CONFIGS = {
     "c272": dict(nx_tile=272, nz=79, layout=(1, 1), dt_atmos=225.0, k_split=2, n_split=6),
     "c768": dict(nx_tile=768, nz=79, layout=(2, 2), dt_atmos=225.0, k_split=2, n_split=6),
 }
+
+
+# moist=True: the names of the first six tracers (the reference's tracer order) and, for the synthetic state, each one's multiple of q_con
+WATER_NAMES = ("qvapor", "qliquid", "qice", "qrain", "qsnow", "qgraupel")
+SYNTHETIC_WATER = dict(qvapor=20.0, qliquid=0.5, qice=0.2, qrain=0.15, qsnow=0.1, qgraupel=0.05)
 
 
 class DycoreHarness:
@@ -72,6 +78,7 @@ class DycoreHarness:
         latlon_winds: bool = False,
         temperature: bool = False,
         vapor: Optional[str] = None,
+        moist: bool = False,
         _testing_token=None,
     ):
         if fill and not remap:
@@ -80,6 +87,14 @@ class DycoreHarness:
             raise ValueError("temperature=True needs remap=True: the conversion back to temperature is the last step of the remap")
         if vapor is not None and not temperature:
             raise ValueError("vapor names the specific-humidity tracer of the temperature conversion: it needs temperature=True")
+        if moist and not temperature:
+            raise ValueError("moist=True needs temperature=True: moist_cv sits in the preamble and the remap of DynamicalCore.step_dynamics")
+        if moist:
+            if vapor not in (None, "qvapor"):
+                raise ValueError(f"moist=True: the specific humidity is the species qvapor (vapor={vapor!r})")
+            vapor = "qvapor"
+            n_tracers = max(int(n_tracers), len(WATER_NAMES))
+        self.moist = bool(moist)
         self.c = get_constants()
         self.part = CubedSpherePartitioner(nx_tile, tuple(layout))
         self.cfg = AcousticDynamicsConfig(npx=nx_tile + 1, npy=nx_tile + 1, npz=nz, layout=tuple(layout), dt_atmos=dt_atmos, k_split=k_split, n_split=n_split,
@@ -131,7 +146,9 @@ class DycoreHarness:
         self.cells_global = nx_tile * nx_tile * 6 * nz
         if temperature:
             self._make_tracers(n_tracers)
-            if vapor is not None and init == "restart":  # the specific humidity the restart's T_v was formed with
+            if moist:
+                self._init_water_species(init, init_data)
+            elif vapor is not None and init == "restart":  # the specific humidity the restart's T_v was formed with
                 self._load_restart_tracer(vapor, init_data, "sphum")
             self._init_temperature(vapor, hord_tr, latlon_winds)
             return
@@ -168,7 +185,31 @@ class DycoreHarness:
         for t in range(n_tracers):
             q = qf.zeros(("x", "y", "z"), "kg/kg")
             q.storage.copy_(self.state.q_con.storage * (10.0 * (t + 1)) + 1.0e-3 * (t + 1))
-            self.tracers[f"tracer{t}"] = q
+            self.tracers[WATER_NAMES[t] if self.moist and t < len(WATER_NAMES) else f"tracer{t}"] = q
+
+    def _init_water_species(self, init, data):
+        """moist=True: the first six tracers are the water species.  ``restart``: qvapor = sphum, qliquid = liq_wat; ``baroclinic``:
+        the humidity of the moist baroclinic wave (pace_amd.init.baroclinic_humidity); the other species zero.  ``synthetic``:
+        fixed positive multiples of the state's q_con field (the condensate shares add up to 1)."""
+        tr, s = self.tracers, self.state
+        if init == "synthetic":
+            for name, share in SYNTHETIC_WATER.items():
+                tr[name].storage.copy_(s.q_con.storage * share)
+            return
+        for name in WATER_NAMES:
+            tr[name].storage.zero_()
+        if init == "restart":
+            self._load_restart_tracer("qvapor", data, "sphum")
+            self._load_restart_tracer("qliquid", data, "liq_wat")
+            return
+        from .init import baroclinic_humidity
+
+        nz = self.cfg.npz
+        for i, g in enumerate(self.grids):
+            delp, peln = s.delp.numpy(i).astype(np.float64), s.peln.numpy(i).astype(np.float64)
+            q = np.zeros(delp.shape)
+            q[:, :, :nz] = baroclinic_humidity(g.lat_agrid, delp[:, :, :nz], peln[:, :, : nz + 1])
+            tr["qvapor"].set_numpy(q, i)
 
     def _load_restart_tracer(self, name, data, key):
         """Tracer ``name`` from the six-tile restart arrays (``data[key][tile][k, y, x]``), placed like the state's cell fields
@@ -188,7 +229,8 @@ class DycoreHarness:
         from .fv_dynamics import DynamicalCore
 
         self.dycore = DynamicalCore(self.layout, self.grids, self.sf, self.sf.quantity_factory, None, self.cfg, self.cfg.dt_atmos, self.state.phis, self.state,
-                                    tracers=self.tracers, hord_tr=hord_tr, vapor=vapor, cubed_to_latlon=latlon_winds)
+                                    tracers=self.tracers, hord_tr=hord_tr, vapor=vapor, cubed_to_latlon=latlon_winds,
+                                    water_species={n: n for n in WATER_NAMES} if self.moist else None)
         d = self.dycore
         self.dyn = d.acoustic_dynamics
         if not self.layout.loopback:
@@ -200,7 +242,8 @@ class DycoreHarness:
 
     def to_temperature(self):
         """The state's ``pt`` from the loop's form ``T_v / pkz`` (what every ``init`` and a default-mode restart file hold) to the
-        temperature in K, ``pkz`` rebuilt from the state, ``ps`` from ``pe``; ``omga`` is not touched."""
+        temperature in K, ``pkz`` rebuilt from the state, ``ps`` from ``pe``; ``omga`` is not touched.  It reads the state's own
+        ``q_con`` / ``cappa`` (also with ``moist``: the species define them from the first preamble on)."""
         s, d = self.state, self.dycore
         d.potential_to_temperature(s.pt, s.pkz, s.delp, s.delz, s.q_con, s.cappa, s.w, s.pe, qvapor=d.qvapor, ps=d.ps, recompute_pkz=True)
 

@@ -348,6 +348,14 @@ def baroclinic_state(grid: GridData, constants: Optional[ConstantSet] = None, pe
     return st
 
 
+def baroclinic_humidity(lat, delp, peln):
+    """Specific humidity of the moist baroclinic wave (FV3 test case 13, test_cases.F90; restated, unpinned):
+    ``q = 0.021 exp(-(lat / (2 pi / 9))^4) exp(-((p_mid - 1e5) / 34000)^2)`` with ``p_mid = delp / (peln[k+1] - peln[k])``.
+    ``lat`` (ni, nj), ``delp`` (ni, nj, nz), ``peln`` (ni, nj, nz + 1)."""
+    p_mid = delp / (peln[:, :, 1:] - peln[:, :, :-1])
+    return 0.021 * np.exp(-((lat[:, :, None] / (2.0 * np.pi / 9.0)) ** 4)) * np.exp(-(((p_mid - 1.0e5) / 34000.0) ** 2))
+
+
 # ---------------------------------------------------------------------------------------------
 # A real FV3 model state: the Fortran restart the reference tree holds (C12, L63, six tiles)
 # [REF tests/main/data/c12_restart/fv_core.res.tile[1-6].nc, fv_tracer.res.tile[1-6].nc; read by the reference through
@@ -359,7 +367,8 @@ def restart_state(grid: GridData, data, tile: int, origin=(0, 0), constants: Opt
     (cells) of tile ``tile``.  As the reference does for a Fortran restart: the prognostic fields are taken as they are
     (u, v, w, delz, delp), pt = T / pkz with the state's own full pressure (non-hydrostatic), pe / peln / pk from ptop + the
     running sum of delp [REF driver/pace/driver/initialization.py:375-395].  q_con = the liquid-water mixing ratio and
-    cappa = kappa (1 - 0.2 q_con) stand in for moist_cv, which is outside this build.  Halos are NOT model data: they
+    cappa = kappa (1 - 0.2 q_con) stand in for moist_cv here (the moist step derives both from the water species:
+    DycoreHarness(moist=True)).  Halos are NOT model data: they
     hold edge-replicated values until the first halo update (every operator of the path exchanges before it reads them)."""
     c = constants or get_constants()
     nh, nx, ny, nz = grid.n_halo, grid.nx, grid.ny, grid.nz

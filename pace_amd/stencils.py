@@ -283,20 +283,31 @@ class LagrangianToEulerian(_Op):
     ``LagrangianToEulerian``, savepoint ``Remapping`` [REF tests/savepoint/thresholds/fv_dynamics.yaml:227-326]).  Call with the
     state's quantities; everything is remapped in place (see ``fv3_remap`` in include/fv3_mi355x.h for the configuration).
     ``fill`` (the namelist's ``fill``, default off): after the remap the negative tracer means are filled in the vertical
-    (:class:`FillNegativeTracerValues` with the Eulerian ``delp``) on the same stream, where the reference runs its ``fillz``."""
+    (:class:`FillNegativeTracerValues` with the Eulerian ``delp``) on the same stream, where the reference runs its ``fillz``.
+    ``water`` (a :class:`WaterSpecies` whose species are among ``tracers``) with ``q_con``: the moist remap ``fv3_remap_moist`` --
+    remap, fill, ``q_con`` / ``cappa`` from the filled species (``moist_cv``), ``pkz`` with the new ``cappa``, FV3's order."""
 
     def __init__(self, stencil_factory, quantity_factory=None, grid_data=None, *args, fill: bool = False, **kw):
         super().__init__(stencil_factory, quantity_factory, grid_data, *args, **kw)
         self.fill = bool(fill)
         self._fillz = FillNegativeTracerValues(stencil_factory, quantity_factory, grid_data) if self.fill else None
 
-    def __call__(self, tracers, pt, delp, delz, peln, pe, pk, pkz, u, v, w, cappa, ps, wsd):
+    def __call__(self, tracers, pt, delp, delz, peln, pe, pk, pkz, u, v, w, cappa, ps, wsd, q_con=None, water=None):
         import ctypes as C
 
         from . import lib as _lib
 
         qs = list(tracers.values()) if tracers else []
         arr = (_lib.F * max(len(qs), 1))(*[C.pointer(q.field) for q in qs])
+        if water is not None:
+            # FV3's order: remap, fill, moist_cv from the filled species, pkz with the new cappa -- all inside the entry
+            if q_con is None:
+                raise ValueError("LagrangianToEulerian: water needs q_con (the moist remap writes it)")
+            st = self.sf.lib.fv3_remap_moist(self.sf.ctx, len(qs), arr, pt.fref, delp.fref, delz.fref, peln.fref, pe.fref, pk.fref, pkz.fref, u.fref, v.fref, w.fref,
+                                             cappa.fref, q_con.fref, ps.fref, wsd.fref, water.cref, 1 if self.fill else 0, self.sf.stream_handle)
+            if st != 0:
+                raise _lib.Fv3Error(f"fv3_remap_moist failed ({st}): " + self.sf.lib.fv3_last_error(self.sf.ctx).decode())
+            return
         st = self.sf.lib.fv3_remap(self.sf.ctx, len(qs), arr, pt.fref, delp.fref, delz.fref, peln.fref, pe.fref, pk.fref, pkz.fref, u.fref, v.fref, w.fref, cappa.fref,
                                    ps.fref, wsd.fref, self.sf.stream_handle)
         if st != 0:
@@ -305,16 +316,80 @@ class LagrangianToEulerian(_Op):
             self._fillz(delp, tracers)  # delp is the Eulerian layer thickness by now: the reference's dp2
 
 
+WATER_ROLES = ("qvapor", "qliquid", "qrain", "qice", "qsnow", "qgraupel")
+
+
+class WaterSpecies:
+    """The six water species of ``moist_cv`` (``fv3_water`` in include/fv3_mi355x.h): ``qvapor`` and up to five optional Quantities
+    (None: a field of zeros) plus the heat capacities ``cv_vap``, ``c_liq``, ``c_ice`` (J/kg/K; defaults: pace_amd.constants)."""
+
+    def __init__(self, qvapor, qliquid=None, qrain=None, qice=None, qsnow=None, qgraupel=None, cv_vap=None, c_liq=None, c_ice=None):
+        import ctypes as C
+
+        from . import constants as _c
+        from . import lib as _lib
+
+        if qvapor is None:
+            raise ValueError("WaterSpecies: qvapor is required (the other five species are optional)")
+        self.species = dict(qvapor=qvapor, qliquid=qliquid, qrain=qrain, qice=qice, qsnow=qsnow, qgraupel=qgraupel)
+        self.cv_vap = float(_c.CV_VAP if cv_vap is None else cv_vap)
+        self.c_liq = float(_c.C_LIQ if c_liq is None else c_liq)
+        self.c_ice = float(_c.C_ICE if c_ice is None else c_ice)
+        self.struct = _lib.fv3_water(*[None if q is None else C.pointer(q.field) for q in self.species.values()], self.cv_vap, self.c_liq, self.c_ice)
+        self.cref = C.byref(self.struct)
+
+    @classmethod
+    def from_tracers(cls, tracers, roles, **constants):
+        """``roles``: {role: tracer name} for the roles of ``WATER_ROLES`` that exist (a missing role is a field of zeros)."""
+        unknown = sorted(set(roles) - set(WATER_ROLES))
+        if unknown:
+            raise ValueError(f"water species roles {unknown}: the roles are {', '.join(WATER_ROLES)}")
+        missing = sorted(n for n in roles.values() if n not in tracers)
+        if missing:
+            raise ValueError(f"water species {missing} are not among the tracers ({', '.join(tracers) or 'none'})")
+        if "qvapor" not in roles:
+            raise ValueError("water species: the role qvapor is required")
+        return cls(**{r: tracers[n] for r, n in roles.items()}, **constants)
+
+    def __getattr__(self, name):
+        if name in WATER_ROLES:
+            return self.species[name]
+        raise AttributeError(name)
+
+
+class MoistCV(_Op):
+    """FV3's ``moist_cv`` for six water species (``fv3_moist_cv``; include/fv3_mi355x.h holds the formulas): ``q_con`` and ``cappa``
+    (and the moist heat capacity ``cvm`` where given) from the species, on the compute cells."""
+
+    def __call__(self, water, q_con, cappa, cvm=None):
+        from . import lib as _lib
+
+        sf = self.sf
+        st = sf.lib.fv3_moist_cv(sf.ctx, water.cref, q_con.fref, cappa.fref, _ref(cvm), sf.stream_handle)
+        if st != 0:
+            raise _lib.Fv3Error(f"fv3_moist_cv failed ({st}): " + sf.lib.fv3_last_error(sf.ctx).decode())
+
+
 class TemperatureToPotential(_Op):
     """The preamble of ``fv_dynamics`` (``fv3_pt_from_temperature`` in include/fv3_mi355x.h holds the formulas): ``pt`` goes from
     the temperature (K) the model state holds between steps to the form the acoustic loop transports, ``T_v / pkz``, and
     ``pkz`` is rebuilt from the full (non-hydrostatic) pressure.  In place on the compute cells; ``delp``, ``delz``, ``q_con``,
-    ``cappa`` and ``qvapor`` (the specific humidity, None: a dry conversion) are only read."""
+    ``cappa`` and ``qvapor`` (the specific humidity, None: a dry conversion) are only read.  With ``water`` (a
+    :class:`WaterSpecies`) ``q_con`` and ``cappa`` are formed from the species in the same kernel and written
+    (``fv3_pt_from_temperature_moist``: bit for bit :class:`MoistCV` followed by the dry call with ``qvapor = water.qvapor``)."""
 
-    def __call__(self, pt, pkz, delp, delz, q_con, cappa, qvapor=None):
+    def __call__(self, pt, pkz, delp, delz, q_con, cappa, qvapor=None, water=None):
         from . import lib as _lib
 
         sf = self.sf
+        if water is not None:
+            # moist_cv inside the cell: q_con and cappa are outputs, qvapor is the species' own
+            if qvapor is not None and qvapor is not water.qvapor:
+                raise ValueError("TemperatureToPotential: qvapor differs from water.qvapor")
+            st = sf.lib.fv3_pt_from_temperature_moist(sf.ctx, pt.fref, pkz.fref, delp.fref, delz.fref, q_con.fref, cappa.fref, water.cref, sf.stream_handle)
+            if st != 0:
+                raise _lib.Fv3Error(f"fv3_pt_from_temperature_moist failed ({st}): " + sf.lib.fv3_last_error(sf.ctx).decode())
+            return
         st = sf.lib.fv3_pt_from_temperature(sf.ctx, pt.fref, pkz.fref, delp.fref, delz.fref, q_con.fref, cappa.fref, _ref(qvapor), sf.stream_handle)
         if st != 0:
             raise _lib.Fv3Error(f"fv3_pt_from_temperature failed ({st}): " + sf.lib.fv3_last_error(sf.ctx).decode())
