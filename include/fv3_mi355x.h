@@ -449,6 +449,41 @@ int fv3_remap_moist(fv3_ctx *, int n_tracers, const fv3_field *const *tracers, c
                     const fv3_field *u, const fv3_field *v, const fv3_field *w, const fv3_field *cappa, const fv3_field *q_con,
                     const fv3_field *ps, const fv3_field *wsd, const fv3_water *water, int fill, void *stream);
 
+/* ---- negative water species (fv3_negadj.hip) ----------------------------------------------------------------------------------
+ * neg_adj3 (FV3 fv_sg.F90, the non-hydrostatic form; pyFV3 AdjustNegativeTracerMixingRatio), which fv_dynamics runs between the last
+ * remap and CubedToLatLon when nwat = 6: a negative condensate is paid for out of another phase with the latent heat booked on the
+ * temperature, negative vapour is repaid from the layer below.  In place on the compute cells 1..nx x 1..ny, levels 0 .. nz-1
+ * (km = nz) of every sub-domain; halo cells and the pad level are neither read nor written; pt is the temperature in K (as
+ * fv3_temperature_from_pt leaves it); dp = delp is only read; q_con and cappa are not touched (the next preamble rebuilds them).
+ * In the build's Real, every sum, product and quotient rounded on its own in the order written.  Constants, formed in double and
+ * cast once: cv_air = cp_air - rdgas (the context's constants); cv_vap, c_liq, c_ice of the fv3_water; d0_vap = cv_vap - c_liq;
+ * lv00 = hlv - (cv_vap - c_liq) * t_ice; dc_ice = c_liq - c_ice; li00 = hlf - (c_liq - c_ice) * t_ice, with the latent heats of
+ * vaporisation and fusion hlv, hlf (J/kg) and the freezing point t_ice (K) of the fv3_latent.
+ *   per cell, from the cell's incoming values:
+ *     q_liq = max(0, ql + qr);  q_sol = max(0, qi + qs)                                       (graupel is not part of q_sol)
+ *     cpm   = (((1 - ((qv + q_liq) + q_sol)) * cv_air + qv * cv_vap) + q_liq * c_liq) + q_sol * c_ice
+ *     lcpk  = (lv00 + d0_vap * pt) / cpm;  icpk = (li00 + dc_ice * pt) / cpm
+ *   then in this order, each test seeing the results of the ones before it:
+ *     qi < 0:  qs = qs + qi;  qi = 0
+ *     qs < 0:  qg = qg + qs;  qs = 0
+ *     qg < 0:  qr = qr + qg;  pt = pt - qg * icpk;  qg = 0
+ *     qr < 0:  ql = ql + qr;  qr = 0
+ *     ql < 0:  qv = qv + ql;  pt = pt - ql * lcpk;  ql = 0
+ *   per column, after the cell step of all its levels, vapour only:
+ *     k = 0 .. km-2 in increasing order, qv[k] < 0:  qv[k+1] = qv[k+1] + (qv[k] * dp[k]) / dp[k+1];  qv[k] = 0
+ *     bottom, qv[km-1] < 0 and qv[km-2] > 0:  dq = min(-qv[km-1] * dp[km-1], qv[km-2] * dp[km-2]);
+ *                                             qv[km-2] = qv[km-2] - dq / dp[km-2];  qv[km-1] = qv[km-1] + dq / dp[km-1]
+ * Comparisons are plain IEEE (-0.0 and NaN take no branch); max(0, x) = x > 0 ? x : 0; min(a, b) = a < b ? a : b.  A value is stored
+ * only where a branch changed it: a column in which no comparison is true is not written at all.
+ * FV3_ERR_ARG (a message that names the field, nothing launched, no field changed): a null context, fv3_water or fv3_latent; any of the
+ * six species NULL (this entry needs all six); a null or wrongly shaped field; a species given twice; pt or delp among the species;
+ * pt == delp.  FV3_ERR_UNSUPPORTED: nz < 2. */
+typedef struct {
+  double hlv, hlf, t_ice;
+} fv3_latent;
+int fv3_neg_adj3(fv3_ctx *, const fv3_water *water, const fv3_latent *latent, const fv3_field *pt, const fv3_field *delp,
+                 void *stream);
+
 /* CubedToLatLon (the last operator of fv_dynamics: FV3 fv_grid_utils.F90 c2l_ord4 / c2l_ord2; pyFV3 CubedToLatLon, savepoint
  * FVDynamics-Out ua / va [REF tests/savepoint/thresholds/fv_dynamics.yaml]).  D-grid u, v -> ua, va on the compute cells in earth
  * coordinates (eastward, northward).  order: c2l_ord, 4 (the reference's default) or 2.  a11 .. a22: the cell-centre rotation

@@ -92,6 +92,11 @@ GEOS = ConstantSet(
 CV_VAP = 3.0 * 461.50
 C_LIQ = 4185.5
 C_ICE = 1972.0
+# Latent heats of vaporisation and fusion (J/kg) and the freezing point (K) of neg_adj3 (fv_sg.F90), run-time data of ``fv3_neg_adj3``
+# (``fv3_latent`` in include/fv3_mi355x.h).  Restated from memory like the heat capacities ("Uncertain restatements").
+HLV = 2.5e6
+HLF = 3.3358e5
+T_ICE = 273.16
 
 _SETS = {"GFS": GFS, "GFDL": GFDL, "GEOS": GEOS}
 

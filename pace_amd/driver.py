@@ -9,7 +9,9 @@ the vertical filling of negative tracer values at the end of the remap with ``dy
 ``--temperature`` (needs ``--remap``) the step is ``DynamicalCore.step_dynamics``: ``pt`` is a temperature in K before and after it,
 ``omga`` and ``ps`` are diagnosed, and the start-up line and the json ``setup`` say ``"pt": "temperature"`` (otherwise ``"loop"``); with ``--moist``
 (needs ``--temperature --remap`` and ``nwat: 6``) the first six tracers are the water species, ``q_con`` and ``cappa`` follow them through
-``moist_cv`` and the start-up line and the json say ``"thermodynamics": "moist_cv"`` (otherwise ``"given"``) -- and writes
+``moist_cv`` and the start-up line and the json say ``"thermodynamics": "moist_cv"`` (otherwise ``"given"``); with ``--neg-adj`` (needs
+``--moist``) FV3's ``neg_adj3`` fixes negative water species after the conversion back to temperature and the start-up line and the json
+say ``"neg_adj": true`` (otherwise ``false``) -- and writes
 the per-step times in the layout the reference's performance collector uses
 (``{"times": {<timer>: {"hits": n, "times": [[...per step...] per rank]}}}``, timers ``mainloop``, ``DynCore``,
 ``TracerAdvection``, ``Remapping`` [REF tests/main/driver/test_driver.py:77-121]).  With ``--tracers N --remap`` the step is the
@@ -138,6 +140,9 @@ def main(argv=None):
     ap.add_argument("--moist", action="store_true",
                     help="derive q_con and cappa from six water species with moist_cv in the preamble and in every remap (needs --temperature --remap and nwat: 6 in the yaml; "
                          "the first six tracers are qvapor, qliquid, qice, qrain, qsnow, qgraupel and --tracers is raised to at least 6)")
+    ap.add_argument("--neg-adj", action="store_true",
+                    help="neg_adj3 at the end of the thermodynamic part of every step (needs --moist): negative condensate is paid for out of another phase with the latent heat "
+                         "booked on the temperature, negative vapour is repaid from the layer below")
     ap.add_argument("--diagnostics-path", default=None, help="directory of the diagnostics (overrides diagnostics_config.path of the yaml)")
     ap.add_argument("--no-diagnostics", action="store_true", help="ignore the yaml's diagnostics_config block")
     a = ap.parse_args(argv)
@@ -145,6 +150,8 @@ def main(argv=None):
         sys.exit("--temperature needs --remap: the conversion back to temperature is the last step of the remap")
     if a.moist and not (a.temperature and a.remap):
         sys.exit("--moist needs --temperature --remap: moist_cv sits in the preamble and the remap of DynamicalCore.step_dynamics")
+    if a.neg_adj and not a.moist:
+        sys.exit("--neg-adj needs --moist: neg_adj3 works on the six water species of the moist step")
     run, dy, ignored = load_config(a.config)
     if a.moist:
         if run["nwat"] is None or int(run["nwat"]) != 6:
@@ -174,6 +181,8 @@ def main(argv=None):
     thermo = "moist_cv" if a.moist else "given"
     say(f'"thermodynamics": "{thermo}"' + ("  (q_con and cappa from qvapor, qliquid, qice, qrain, qsnow, qgraupel in the preamble and in every remap)" if a.moist
                                          else "  (q_con and cappa are the state's fields as initialised; --moist --temperature --remap: moist_cv of six water species)"))
+    say(f'"neg_adj": {str(bool(a.neg_adj)).lower()}' + ("  (neg_adj3 on the temperature and the six water species after the last remap of every step)" if a.neg_adj
+                                                         else "  (negative water species stay as the remap leaves them; --moist --neg-adj: neg_adj3)"))
     if run["init"] == "analytic" and str(run["case"]).startswith("baroclinic"):
         init = "baroclinic"
         say("initialization: JW2006 baroclinic wave (pace_amd.init.baroclinic_state; restated from the paper, see its docstring)")
@@ -195,7 +204,7 @@ def main(argv=None):
     kw = {k: dy[k] for k in ("k_split", "n_split") if k in dy}
     h = DycoreHarness(nx_tile=run["nx_tile"], nz=run["nz"], layout=run["layout"], dt_atmos=run["dt_atmos"], world_size=world, proc=rank,
                       device=f"cuda:{local_rank}", dtype=dtype, verbose=(rank == 0), init=init, config_overrides={k: v for k, v in dy.items() if k not in ("k_split", "n_split", "fill")},
-                      n_tracers=a.tracers, hord_tr=int(dy.get("hord_tr", 8)), remap=a.remap, fill=fill, latlon_winds=a.latlon_winds, temperature=a.temperature, moist=a.moist, **kw)
+                      n_tracers=a.tracers, hord_tr=int(dy.get("hord_tr", 8)), remap=a.remap, fill=fill, latlon_winds=a.latlon_winds, temperature=a.temperature, moist=a.moist, neg_adj=a.neg_adj, **kw)
     if run["device_sync"]:
         h.sf.set_device_sync(True)
     if a.restart:
@@ -282,17 +291,18 @@ def main(argv=None):
         sdpd = run["dt_atmos"] / mean
         out = a.out or f"{run['experiment']}_fv3_mi355x.json"
         json.dump({"setup": {"experiment": run["experiment"], "nx_tile": run["nx_tile"], "nz": run["nz"], "layout": list(run["layout"]), "dt_atmos": run["dt_atmos"],
-                             "k_split": h.cfg.k_split, "n_split": h.cfg.n_split, "n_gpus": world, "backend": "hip:gfx950", "dycore_only": True, "acoustic_only": not (a.tracers or a.remap), "tracers": a.tracers, "remap": bool(a.remap), "fill": fill, "pt": pt_form, "thermodynamics": thermo, "finite": ok,
+                             "k_split": h.cfg.k_split, "n_split": h.cfg.n_split, "n_gpus": world, "backend": "hip:gfx950", "dycore_only": True, "acoustic_only": not (a.tracers or a.remap), "tracers": a.tracers, "remap": bool(a.remap), "fill": fill, "pt": pt_form, "thermodynamics": thermo, "neg_adj": bool(a.neg_adj), "finite": ok,
                              "note": ("a step here is k_split AcousticDynamics calls; the reference's dycore_only mainloop (DynamicalCore.step_dynamics) also runs tracer "
                                       "advection and the Lagrangian-to-Eulerian remap (--tracers N --remap add them): not comparable with the reference's 'mainloop' timer")
                              if not (a.tracers and a.remap) else
                              "a step is k_split x [AcousticDynamics, tracer advection, vertical remap] = the body of DynamicalCore.step_dynamics without physics and "
-                             + ("the saturation adjustment (q_con and cappa follow the six water species: moist_cv)" if a.moist else "moist thermodynamics")},
+                             + (("the saturation adjustment (q_con and cappa follow the six water species: moist_cv" + ("; neg_adj3 fixes negative species)" if a.neg_adj else "; neg_adj3 is left out: --neg-adj)"))
+                                if a.moist else "moist thermodynamics")},
                    # the reference collector's layout: times.<timer> = {hits, times[rank][step]}; "mainloop" only when the step is the
                    # whole body of step_dynamics (--tracers N --remap), then .jenkins/print_performance_number.py runs on this file as is
                    "times": report,
                    "times_note": ("only the outer clock ('" + loop_name + "') synchronises the device; the nested clocks (DynCore / TracerAdvection / Remapping) are host-side "
-                                  "enqueue intervals. " + (("'mainloop' here = the body of step_dynamics with moist_cv of six water species: no saturation adjustment, no physics coupling "
+                                  "enqueue intervals. " + (("'mainloop' here = the body of step_dynamics with moist_cv of six water species" + (" and neg_adj3" if a.neg_adj else "") + ": no saturation adjustment, " + ("" if a.neg_adj else "no neg_adj3, ") + "no physics coupling "
                                                             "-- the reference's mainloop does more per step." if a.moist else
                                                             "'mainloop' here = the dry body of step_dynamics with N synthetic tracers: no moist thermodynamics, no physics coupling "
                                                             "-- the reference's mainloop does more per step.") if full_step else "")),

@@ -10,7 +10,9 @@ The contract of the call is the reference's: ``state.pt`` holds the temperature 
    vertical filling where ``config.fill`` asks for it ("Remapping") -- the sequence of ``DycoreHarness.step``,
 3. :class:`~pace_amd.stencils.PotentialToTemperature` takes ``pt`` back to K with the ``pkz`` the last remap left, diagnoses
    ``state.omga = delp / delz * w`` and the surface pressure ``DynamicalCore.ps``,
-4. :class:`~pace_amd.stencils.CubedToLatLon`, where asked ("CubedToLatLon").
+4. :class:`~pace_amd.stencils.AdjustNegativeTracerMixingRatio`, where asked (``adjust_negative_water``; "NegAdj3"): FV3's
+   ``neg_adj3`` on the temperature and the six water species,
+5. :class:`~pace_amd.stencils.CubedToLatLon`, where asked ("CubedToLatLon").
 
 Without ``water_species`` ``q_con`` and ``cappa`` are fields of the state that the caller provides.  With it they are derived from
 the six water species by FV3's ``moist_cv`` where FV3 derives them: step 1 becomes the moist preamble
@@ -49,6 +51,7 @@ class DynamicalCore:
         vapor: Optional[str] = None,
         cubed_to_latlon: bool = True,
         water_species: Optional[Dict[str, str]] = None,
+        adjust_negative_water: bool = False,
     ):
         """Arguments as the reference's call.  ``comm``: a :class:`pace_amd.halo.Layout` (None: every rank in this process);
         ``timestep``: the model step ``dt_atmos`` in seconds or as a ``timedelta`` (None: ``config.dt_atmos``); ``tracers``:
@@ -57,7 +60,9 @@ class DynamicalCore:
         transport scheme; ``cubed_to_latlon``: end the step with the eastward / northward ``ua``, ``va``; ``water_species``:
         ``{role: tracer name}`` for the roles ``qvapor``, ``qliquid``, ``qrain``, ``qice``, ``qsnow``, ``qgraupel`` (a missing role is a
         field of zeros; ``qvapor`` is required and becomes ``vapor``) -- ``q_con`` and ``cappa`` are then derived from these tracers
-        (``moist_cv``) in the preamble and in every remap; None: they are the state's fields as the caller left them."""
+        (``moist_cv``) in the preamble and in every remap; None: they are the state's fields as the caller left them;
+        ``adjust_negative_water``: run ``neg_adj3`` on ``state.pt`` and the species after the conversion back to temperature (FV3 does
+        whenever ``nwat == 6``); it needs ``water_species`` with all six roles."""
         sf = stencil_factory
         qf = quantity_factory or sf.quantity_factory
         self.sf, self.qf = sf, qf
@@ -91,6 +96,12 @@ class DynamicalCore:
         self.temperature_to_potential = st.TemperatureToPotential(sf, qf, grid_data)
         self.potential_to_temperature = st.PotentialToTemperature(sf, qf, grid_data)
         self.cubed_to_latlon = st.CubedToLatLon(sf, qf, grid_data, order=self.config.c2l_ord, comm=self.layout) if cubed_to_latlon else None
+        self.adjust_negative_water = None
+        if adjust_negative_water:
+            missing = [r for r in st.WATER_ROLES if r not in (water_species or {})]
+            if missing:
+                raise ValueError(f"adjust_negative_water=True needs water_species with all six roles (missing: {', '.join(missing)})")
+            self.adjust_negative_water = st.AdjustNegativeTracerMixingRatio(sf, qf, grid_data)
 
     @property
     def qvapor(self) -> Optional[Quantity]:
@@ -98,7 +109,8 @@ class DynamicalCore:
 
     def step_dynamics(self, state: DycoreState, timer=None):
         """One model step: ``state.pt`` is a temperature (K) on entry and on return.  ``timer`` (pace_amd.timer.Timer): the
-        reference's clocks "DynCore", "TracerAdvection", "Remapping", "CubedToLatLon" [REF tests/main/driver/test_driver.py:77-121]."""
+        reference's clocks "DynCore", "TracerAdvection", "Remapping", "CubedToLatLon" [REF tests/main/driver/test_driver.py:77-121] and this
+        build's "NegAdj3"."""
         from .timer import NullTimer
 
         timer = timer or NullTimer()
@@ -120,6 +132,9 @@ class DynamicalCore:
                 self.remap(tracers, s.pt, s.delp, s.delz, s.peln, s.pe, s.pk, s.pkz, s.u, s.v, s.w, s.cappa, self.ps, dyn._wsd, q_con=s.q_con, water=water)
         # the last-step conversion of the remap: pkz is the one the remap has just formed with these delp, delz and T_v
         self.potential_to_temperature(s.pt, s.pkz, s.delp, s.delz, s.q_con, s.cappa, s.w, s.pe, qvapor=qv, omga=s.omga, ps=self.ps, recompute_pkz=False)
+        if self.adjust_negative_water is not None:
+            with timer.clock("NegAdj3"):
+                self.adjust_negative_water(pt=s.pt, delp=s.delp, water=water)
         if self.cubed_to_latlon is not None:
             with timer.clock("CubedToLatLon"):
                 self.cubed_to_latlon(s.u, s.v, s.ua, s.va)

@@ -10,7 +10,8 @@ tracer values at the end of the remap (the namelist's ``fill``); ``latlon_winds`
 ends ``fv_dynamics`` (eastward / northward ``ua``, ``va``); ``temperature`` (needs ``remap``) makes the step
 ``DynamicalCore.step_dynamics`` (pace_amd/fv_dynamics.py): ``state.pt`` is then a temperature in K between steps, ``omga`` and ``ps`` are
 diagnosed, ``vapor`` names the tracer that is the specific humidity; ``moist`` (needs ``temperature``) names the first six tracers
-after the water species and lets ``q_con`` / ``cappa`` follow them (``moist_cv`` in the preamble and in every remap).
+after the water species and lets ``q_con`` / ``cappa`` follow them (``moist_cv`` in the preamble and in every remap); ``neg_adj``
+(needs ``moist``) ends the thermodynamic part of the step with FV3's ``neg_adj3`` on the temperature and the six species.
 """
 from __future__ import annotations
 
@@ -79,6 +80,7 @@ class DycoreHarness:
         temperature: bool = False,
         vapor: Optional[str] = None,
         moist: bool = False,
+        neg_adj: bool = False,
         _testing_token=None,
     ):
         if fill and not remap:
@@ -89,6 +91,9 @@ class DycoreHarness:
             raise ValueError("vapor names the specific-humidity tracer of the temperature conversion: it needs temperature=True")
         if moist and not temperature:
             raise ValueError("moist=True needs temperature=True: moist_cv sits in the preamble and the remap of DynamicalCore.step_dynamics")
+        if neg_adj and not moist:
+            raise ValueError("neg_adj=True needs moist=True: neg_adj3 works on the six water species of the moist step")
+        self.neg_adj = bool(neg_adj)
         if moist:
             if vapor not in (None, "qvapor"):
                 raise ValueError(f"moist=True: the specific humidity is the species qvapor (vapor={vapor!r})")
@@ -230,7 +235,7 @@ class DycoreHarness:
 
         self.dycore = DynamicalCore(self.layout, self.grids, self.sf, self.sf.quantity_factory, None, self.cfg, self.cfg.dt_atmos, self.state.phis, self.state,
                                     tracers=self.tracers, hord_tr=hord_tr, vapor=vapor, cubed_to_latlon=latlon_winds,
-                                    water_species={n: n for n in WATER_NAMES} if self.moist else None)
+                                    water_species={n: n for n in WATER_NAMES} if self.moist else None, adjust_negative_water=self.neg_adj)
         d = self.dycore
         self.dyn = d.acoustic_dynamics
         if not self.layout.loopback:

@@ -114,6 +114,10 @@ class fv3_water(C.Structure):
     _fields_ = [(n, F) for n in "qvapor qliquid qrain qice qsnow qgraupel".split()] + [(n, C.c_double) for n in "cv_vap c_liq c_ice".split()]
 
 
+class fv3_latent(C.Structure):
+    _fields_ = [(n, C.c_double) for n in "hlv hlf t_ice".split()]
+
+
 _D = C.c_double
 _I = C.c_int
 _S = C.c_void_p  # stream
@@ -177,6 +181,7 @@ _PROTOS = {
     "fv3_moist_cv": (C.c_int, [C.c_void_p, P(fv3_water), F, F, F, _S]),
     "fv3_pt_from_temperature_moist": (C.c_int, [C.c_void_p] + [F] * 6 + [P(fv3_water), _S]),
     "fv3_remap_moist": (C.c_int, [C.c_void_p, _I, P(F)] + [F] * 14 + [P(fv3_water), _I, _S]),
+    "fv3_neg_adj3": (C.c_int, [C.c_void_p, P(fv3_water), P(fv3_latent), F, F, _S]),
     "fv3_cubed_to_latlon": (C.c_int, [C.c_void_p, _I] + [F] * 8 + [_S]),
     "fv3_diag_pack": (C.c_int, [C.c_void_p, F, _I, _I, _I, _I, C.c_void_p, C.c_long, _S]),
     "fv3_diag_column_integral": (C.c_int, [C.c_void_p, F, F, C.c_void_p, C.c_long, _S]),

@@ -370,6 +370,50 @@ class MoistCV(_Op):
             raise _lib.Fv3Error(f"fv3_moist_cv failed ({st}): " + sf.lib.fv3_last_error(sf.ctx).decode())
 
 
+class AdjustNegativeTracerMixingRatio(_Op):
+    """``neg_adj3`` (FV3 ``fv_sg.F90``; the pyFV3 operator of this name), which ``fv_dynamics`` runs between the last remap and
+    ``CubedToLatLon`` when ``nwat = 6``: a negative condensate is paid for out of another phase with the latent heat booked on the
+    temperature ``pt`` (K), negative vapour is repaid from the layer below (``fv3_neg_adj3`` in include/fv3_mi355x.h holds the
+    algorithm).  In place on the compute cells; ``delp`` is only read.  The non-hydrostatic form only.  ``hlv``, ``hlf``, ``t_ice``:
+    the latent heats of vaporisation and fusion (J/kg) and the freezing point (K) (defaults: pace_amd.constants).
+
+    Call as the reference's ``(qvapor, qliquid, qrain, qsnow, qice, qgraupel, qcld, pt, delp, delz, peln)``: ``qcld`` must be None
+    (the cloud-fraction fix is not part of this build); ``delz`` and ``peln`` are accepted and not read.  ``water=`` (a
+    :class:`WaterSpecies` with all six species) takes the place of the six positional species."""
+
+    def __init__(self, stencil_factory, quantity_factory=None, grid_data=None, *, hydrostatic=False, hlv=None, hlf=None, t_ice=None):
+        import ctypes as C
+
+        from . import constants as _c
+        from . import lib as _lib
+
+        super().__init__(stencil_factory, quantity_factory, grid_data)
+        if hydrostatic:
+            raise NotImplementedError("AdjustNegativeTracerMixingRatio: only the non-hydrostatic form of neg_adj3 is built")
+        self.hlv = float(_c.HLV if hlv is None else hlv)
+        self.hlf = float(_c.HLF if hlf is None else hlf)
+        self.t_ice = float(_c.T_ICE if t_ice is None else t_ice)
+        self.latent = _lib.fv3_latent(self.hlv, self.hlf, self.t_ice)
+        self._lref = C.byref(self.latent)
+
+    def __call__(self, qvapor=None, qliquid=None, qrain=None, qsnow=None, qice=None, qgraupel=None, qcld=None, pt=None, delp=None, delz=None, peln=None, *, water=None):
+        from . import lib as _lib
+
+        if qcld is not None:
+            raise NotImplementedError("AdjustNegativeTracerMixingRatio: the cloud-fraction fix of neg_adj3 is not built, so qcld must be None")
+        species = (qvapor, qliquid, qrain, qsnow, qice, qgraupel)
+        if water is None:
+            water = WaterSpecies(qvapor, qliquid=qliquid, qrain=qrain, qice=qice, qsnow=qsnow, qgraupel=qgraupel)
+        elif any(q is not None for q in species):
+            raise ValueError("AdjustNegativeTracerMixingRatio: give the six species or water=, not both")
+        if pt is None or delp is None:
+            raise ValueError("AdjustNegativeTracerMixingRatio: pt and delp are required")
+        sf = self.sf
+        st = sf.lib.fv3_neg_adj3(sf.ctx, water.cref, self._lref, pt.fref, delp.fref, sf.stream_handle)
+        if st != 0:
+            raise _lib.Fv3Error(f"fv3_neg_adj3 failed ({st}): " + sf.lib.fv3_last_error(sf.ctx).decode())
+
+
 class TemperatureToPotential(_Op):
     """The preamble of ``fv_dynamics`` (``fv3_pt_from_temperature`` in include/fv3_mi355x.h holds the formulas): ``pt`` goes from
     the temperature (K) the model state holds between steps to the form the acoustic loop transports, ``T_v / pkz``, and
