@@ -80,6 +80,9 @@ class StencilFactory:
 
     def _create(self):
         s = self.sizer
+        if s.n_sub > _lib.FV3_MAX_SUB:
+            raise ValueError(f"{s.n_sub} sub-domains in one process: a context holds at most FV3_MAX_SUB = {_lib.FV3_MAX_SUB}; this layout needs more processes "
+                             f"(at least {-(-s.n_sub // _lib.FV3_MAX_SUB)} times as many)")
         spec = _lib.fv3_gridspec()
         spec.nx, spec.ny, spec.nz, spec.n_halo, spec.n_sub = s.nx, s.ny, s.nz, s.n_halo, s.n_sub
         for t, g in enumerate(self.grids):

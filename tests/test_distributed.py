@@ -1,5 +1,6 @@
 """The N > 1 path on CPU: two gloo processes, each owning half of the cube's sub-domains
-(hostemu kernels), must reproduce the single-process result bit for bit."""
+(hostemu kernels), must reproduce the single-process result bit for bit -- and the message path (pack order, message layout, unpack order) must put
+into every halo point of every process what the geometric reference (tests/halo_reference.py) says, halo included."""
 import os
 import sys
 
@@ -159,3 +160,52 @@ def test_halo_exchanger_reports_a_released_factory_and_a_foreign_group(hostemu):
     gc.collect()
     with pytest.raises(RuntimeError, match="has been released"):
         ex.sf
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The message path against the geometric reference: coded fields (tests/halo_exchange_case.py), every halo point of every process
+# ---------------------------------------------------------------------------------------------------------------------------
+def _halo_worker(rank, world, init_file, out_dir, nx_tile, layout, native):
+    import json
+
+    for p in (ROOT, os.path.join(ROOT, "tests")):
+        sys.path.insert(0, p)
+    os.environ["FV3_HALO_NATIVE"] = native
+    import torch.distributed as dist
+
+    import halo_exchange_case as hc
+
+    torch.set_num_threads(1)
+    os.environ["OMP_NUM_THREADS"] = "2"
+    dist.init_process_group("gloo", init_method=f"file://{init_file}", rank=rank, world_size=world)
+    # one scalar updater with two groups, one dgrid updater, one corner updater and the sync; every one checked bitwise on this process's own ranks
+    got = hc.run_distributed("hostemu", torch.float64, nx_tile, layout, 7, world, rank)
+    json.dump(got, open(os.path.join(out_dir, f"halo{rank}.json"), "w"))
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+# layout 3x3 is the only one with a sub-domain that touches no tile edge; its 54 sub-domains need two processes or more (27 each: under the 32 of a context).
+# It runs at C18, the smallest cube it can be built on: a context refuses sub-domains of fewer than 6 x 6 cells, which C12 / 3 = 4 would be (the maps
+# of C12 layout 3x3 and 4x4 are compared with the reference in tests/test_halo_exchange.py, which needs no context).
+@pytest.mark.parametrize("native", ["1", "0"])
+@pytest.mark.parametrize("n, layout, world", [(12, (2, 2), 2), (12, (2, 2), 8), (18, (3, 3), 2), (18, (3, 3), 6)])
+def test_messages_between_processes_fill_every_halo_point_as_the_reference_says(hostemu, tmp_path, n, layout, world, native, monkeypatch):
+    import json
+
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import halo_exchange_case as hc
+
+    monkeypatch.setenv("FV3_HALO_NATIVE", native)
+    mp.spawn(_halo_worker, args=(world, str(tmp_path / "init"), str(tmp_path), n, layout, native), nprocs=world, join=True)
+    total = 0
+    for p in range(world):
+        got = json.load(open(tmp_path / f"halo{p}.json"))
+        want = hc.distributed_counts(n, layout, world, p)
+        assert got == want, (p, got, want)
+        total += sum(got.values())
+    # the whole cube, closed form: per rank and component the depth-3 frame, minus the 24 blocks of 9 beyond the cube corners; the sync: nx + ny per rank
+    lx, ly = layout
+    nx, ny, ranks = n // lx, n // ly, 6 * lx * ly
+    frame = lambda ex, ey: ranks * ((ex + 6) * (ey + 6) - ex * ey) - 24 * 9  # noqa: E731
+    assert total == 2 * frame(nx, ny) + frame(nx, ny + 1) + frame(nx + 1, ny) + frame(nx + 1, ny + 1) + ranks * (nx + ny)

@@ -148,6 +148,29 @@ def test_two_process_decomposition_is_bitwise_identical(tmp_path, nx, layout, wo
 
 
 @pytest.mark.gpu
+def test_two_process_messages_fill_every_halo_point_as_the_reference_says(tmp_path):
+    """C12 layout 2x2 on two processes (gloo staged through pinned host memory): coded fields through one scalar updater with two groups, one dgrid
+    updater, one corner updater and the interface sync; every process compares the whole storage of its own 12 sub-domains, halo included, with the
+    geometric reference bit for bit (tests/halo_exchange_case.py, the worker of tests/test_distributed.py's cases)."""
+    import json
+    import sys
+
+    import halo_exchange_case as hc
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    tool = os.path.join(root, "tests", "halo_exchange_case.py")
+    env = dict(os.environ, FV3_FORCE_DEVICE="0", HSA_ENABLE_IPC_MODE_LEGACY="0")
+    out = str(tmp_path / "halo.json")
+    _run(
+        [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", _free_port(),
+         tool, "--backend", "hip:gfx950", "--distributed", "--nx", "12", "--layout", "2", "--out", out],
+        check=True, env=env, timeout=300,
+    )
+    got = json.load(open(out))
+    assert got == [hc.distributed_counts(12, (2, 2), 2, p) for p in range(2)], got
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize(
     "toggle",
     ["FV3_RIEM_MODE=columns", "FV3_EDGE_PROFILE_LDS=1", "FV3_EDGE_PROFILE_REG=1", "FV3_EDGE_PROFILE_GENERIC=1", "FV3_TP2D_MODE=staged", "FV3_DEL6_MODE=staged", "FV3_SEG=96", "FV3_SEG=32", "FV3_CSW_B_GENERIC=1", "FV3_CSW_MARCH=0", "FV3_CSW_MARCH=abc", "FV3_DIVDAMP_STAGED=1", "FV3_KE_STAGED=1", "FV3_DSW_SCALARS=separate", "FV3_AUX_STREAM=0", "FV3_GRID_SPLIT=0", "FV3_PINGPONG=0", "FV3_DSW_WIND_OVERLAP=1", "FV3_TP2D_FA=0", "FV3_RIEM_REGS=0", "FV3_DSW_MARCH=old", "FV3_TP2D_MARCH=old", "FV3_DSW_HEAT=separate", "FV3_CSW_WIN_OVERLAP=0", "FV3_ACC_STORE=0", "FV3_EP_ONE_LAUNCH=0", "FV3_DSW_WINDSTAGE=staged", "FV3_DSW_MARCH=coupled", "FV3_CSW_DEFER=1", "FV3_DEL2_FUSED=0", "FV3_DEL2_HEAT=fused", "FV3_GZ_FIRST=copy", "FV3_DSW_VORT_IN_KE=1", "FV3_DSW_SIDE=copy", "FV3_DSW_SPONGE_WIND=serial", "FV3_FRAME_LAUNCH=split", "FV3_GATHER_BATCH=0", "FV3_DZ_SCAN=separate", "FV3_SEQ_DELZ=every", "FV3_SEQ_UAVA=every", "FV3_ACC_DEFER=0"],
