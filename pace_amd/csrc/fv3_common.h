@@ -213,6 +213,34 @@ struct DampTables {
   const Real *dd8;    // (da_min_c * d4_bg)^(nord+1)     divergence damping
 };
 
+// What fv3_acoustic_step tells an operator about the ONE call it is making (fv3_ctx::seq, installed and taken back by SeqScope in fv3_step.hip).
+// Every default is "stand-alone operator": a call from outside the sequencer never sees anything else.
+struct fv3_seq_hints {
+  // d_sw: the workspace divgd is dead after the operator (the next c_sw overwrites it)
+  bool divgd_dead = false;
+  // d_sw of a call's FIRST sub-step: mfx, mfy, cx, cy hold nothing yet -- d_sw forms 0 + flux with the zero read from fv3_ctx::zeros, not from the field
+  bool acc_first = false;
+  // ... the same for the accumulated damping heat (heat_source): d_sw's two heat sites form 0 + heat
+  bool heat_first = false;
+  // c_sw: it may leave its last boundary-window launches (stages D and E: they write window cells of delpc / ptc / wc / ke / vort / uc / vc, which update_dz_c
+  // does not touch) RUNNING on the auxiliary stream when it returns (fv3_ctx::csw_pending); the sequencer joins them before riem_solver_c, the first reader
+  bool csw_defer = false;
+  // update_dz_d: it may leave its last kernel -- the bottom-up scan that keeps the marched interface heights dz_min apart and forms the surface vertical
+  // velocity -- to riem_solver3, whose wave form runs it as a pre-sweep of each column (fv3_nh.hip: PRE; fv3_ctx::dz_scan_src)
+  bool dz_scan = false;
+  // d_sw: leave cx / cy alone -- crx / cry of every sub-step of a call stay in their own arrays (fv3_ctx::acc_slots) and cx / cy are formed ONCE, at the end of
+  // the last d_sw of the call, as ((0 + s1) + s2) + ... in the order the read-modify-write of every sub-step would have used
+  bool acc_defer = false;
+  int acc_sum_n = 0;  // > 0: this d_sw call is the last of the acoustic call -- it ends with the sum of that many sub-steps' arrays into the accumulators
+  // c_sw: not the last of the call -- ua / va are read by d_sw's divergence (levels without a damping chain) and c_sw's own boundary windows only
+  bool uava_thin = false;
+  // riem_solver3: not the last of the acoustic call -- nobody reads the layer thickness it would store (the next sub-step works from zh)
+  bool delz_dead = false;
+  // Frame-first passes of the operators that feed a halo update (p_grad_c, riem_solver3, nh_p_grad + ray_fast): 0: whole box; 1: the frame of every
+  // sub-domain only (the cells a neighbour's halo is packed from); 2: the interior only
+  int frame_pass = 0;
+};
+
 struct fv3_ctx {
   Geo g;
   const Geo *g_dev = nullptr;  // device-resident copy of g: rarely taken kernel paths read geometry through it
@@ -261,41 +289,19 @@ struct fv3_ctx {
   // registered halo plans apply while the state lives in the alternates.
   Real *pp_buf[4] = {nullptr, nullptr, nullptr, nullptr};
   int pp_state = 0;
-  // set by fv3_acoustic_step around its d_sw call: the workspace divgd is dead after the operator (the next c_sw overwrites it)
-  bool seq_divgd_dead = false;
-  // set by fv3_acoustic_step around the d_sw call of a call's FIRST sub-step: the four accumulators of the tracer sub-cycling (mfx, mfy, cx, cy) hold
-  // nothing yet, so d_sw forms 0 + flux with the zero read from `zeros` (one level plane of zeros, 1.2 MB at C768: it stays in L2) instead of the field, and the sequencer
-  // zeroes only the cells d_sw never writes (zero_unwritten, fv3_step.hip: every call, no cached state; FV3_ACC_STORE=0: zero + accumulate on every sub-step, as the reference does -- same values).
-  bool seq_acc_first = false;
-  // set by fv3_acoustic_step around c_sw: the operator may leave its last boundary-window launches (stages D and E: they write window cells of delpc / ptc / wc /
-  // ke / vort / uc / vc, which update_dz_c does not touch) RUNNING on the auxiliary stream when it returns; csw_pending then says that the join (event 7) is still
-  // owed -- the sequencer pays it before riem_solver_c, the first reader (fv3_csw_join).  The stand-alone operator always joins before it returns.
-  bool seq_csw_defer = false;
-  bool csw_pending = false;
-  // Round 6: inside the sequencer update_dz_d leaves its last kernel -- the bottom-up scan that keeps the marched interface heights dz_min apart and forms
-  // the surface vertical velocity -- to riem_solver3, whose wave form runs it as a pre-sweep of each column (fv3_nh.hip: PRE).  seq_dz_scan: the sequencer
-  // allows it for the update_dz_d call it is about to make; dz_scan_src: the marched heights of a scan still to be done (null: none); dz_scan_min: dz_min.
-  bool seq_dz_scan = false;
-  // Round 6, deferred accumulation of the Courant numbers (fv3_step.hip): inside the sequencer crx / cry of every sub-step of a call stay in their own arrays
-  // (acc_slots: crx, cry per sub-step -- fields fxadv writes anyway) and cx / cy are formed ONCE, at the end of the last d_sw of the call, as ((0 + s1) + s2) + ...
-  // in the order the read-modify-write of every sub-step would have used.  seq_acc_defer: the sequencer asks the d_sw call it is about to make not to touch cx / cy.
-  std::vector<Real *> acc_slots;
-  int acc_state = 0;  // -1: the slots could not be allocated (or FV3_ACC_DEFER=0): read-modify-write in every sub-step
-  bool seq_acc_defer = false;
-  int seq_acc_sum_n = 0;  // > 0: this d_sw call is the last of the acoustic call -- it ends with the sum of that many sub-steps' arrays into the accumulators
-  bool seq_uava_thin = false;  // the sequencer: this c_sw call is not the last of the acoustic call -- its A-grid winds are read by d_sw's divergence on the levels without a damping chain and by c_sw's own boundary windows next to the march's rectangle, nowhere else
-  bool seq_delz_dead = false;  // the sequencer: this riem_solver3 call is not the last of the acoustic call -- nobody reads the layer thickness it would store (the next sub-step works from zh)
-  Real *dz_scan_src = nullptr;
-  Real dz_scan_min = (Real)0;
-  bool seq_heat_first = false;  // ... the same for the accumulated damping heat (heat_source): d_sw's two heat sites form 0 + heat on the call's first sub-step
-  Real *zeros = nullptr;
   const void *pp_from[4] = {nullptr, nullptr, nullptr, nullptr};
   void *pp_to[4] = {nullptr, nullptr, nullptr, nullptr};
   int pp_n = 0;
-  // Frame-first passes (fv3_step.hip): the operators that feed a halo update (p_grad_c -> uc / vc; nh_p_grad + ray_fast -> u / v / w)
-  // run their last kernel on the frame of every sub-domain first (the cells a neighbour's halo is packed from), the update starts,
-  // and the interior follows while the messages travel.  0: whole box (default); 1: frame only; 2: interior only.
-  int frame_pass = 0;
+  fv3_seq_hints seq;  // what fv3_acoustic_step says about the operator call it is making (fv3_step.hip: SeqScope); all defaults outside it
+  bool csw_pending = false;  // c_sw under seq.csw_defer left stage D / E windows running on the auxiliary stream: the join (event 7, fv3_csw_join) is still owed
+  // Channel from update_dz_d to riem_solver3 (fv3_nh.hip), not a hint: update_dz_d under seq.dz_scan WRITES the marched heights of the scan it left undone
+  // (null: none) and dz_min; riem_solver3's wave form READS them, runs the scan as its pre-sweep and CLEARS dz_scan_src; so does every way out of the sequencer
+  Real *dz_scan_src = nullptr;
+  Real dz_scan_min = (Real)0;
+  // Deferred accumulation of the Courant numbers (seq.acc_defer): crx, cry of every sub-step of a call, in arrays of their own (fields fxadv writes anyway)
+  std::vector<Real *> acc_slots;
+  int acc_state = 0;  // -1: the slots could not be allocated (or FV3_ACC_DEFER=0): read-modify-write in every sub-step
+  Real *zeros = nullptr;  // one level plane of zeros (1.2 MB at C768: it stays in L2): what seq.acc_first / seq.heat_first add the flux to
   // per-operator profiling (fv3_step.hip)
   int profiling = 0;
   struct ProfEvent {

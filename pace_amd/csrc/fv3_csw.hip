@@ -755,7 +755,7 @@ extern "C" int fv3_c_sw(fv3_ctx *c, const fv3_field *delp_, const fv3_field *pt_
   // the generic form then only runs on four windows along the sub-domain boundary (and skips the interior).
   if (fused) {
     // (FV3_SEQ_UAVA=every: ua / va stored in full by every sub-step, A/B; read per call)
-    csw_fused_stream(c, s, u, v, delp, pt, w, ua, va, uc, vc, ut, vt, divgd, delpc, ptc, omga, ke, vort, dt2, nord > 0, c->seq_uava_thin && !fv3_sw_is(FV3SW_SEQ_UAVA, "every"));
+    csw_fused_stream(c, s, u, v, delp, pt, w, ua, va, uc, vc, ut, vt, divgd, delpc, ptc, omga, ke, vort, dt2, nord > 0, c->seq.uava_thin && !fv3_sw_is(FV3SW_SEQ_UAVA, "every"));
   } else if (march) {
     csw_abc_stream(c, s, u, v, ua, va, uc, vc, ut, vt, divgd, dt2, nord > 0);
   } else if (b_split) {
@@ -1158,7 +1158,7 @@ extern "C" int fv3_c_sw(fv3_ctx *c, const fv3_field *delp_, const fv3_field *pt_
   // riem_solver_c -- the first reader of the windows' delpc / ptc / wc -- is where the sequencer joins (fv3_csw_join).  Same values; c_sw shrinks by 1.1 ms and
   // update_dz_c, bandwidth-bound beside the windows, grows by 0.85: four same-box pairs gave -0.7 / -0.0 / +0.6 / +0.1 ms per sub-step.  Events 6 = fork, 7 = join.
   static const bool defer_on = fv3_sw(FV3SW_CSW_DEFER);
-  fv3_stream_t sd_ = (fused && defer_on && c->seq_csw_defer) ? fv3_aux(c, s) : s;
+  fv3_stream_t sd_ = (fused && defer_on && c->seq.csw_defer) ? fv3_aux(c, s) : s;
   if (sd_ != s) {
     fv3_signal(c, s, 6);
     fv3_wait(c, sd_, 6);
@@ -1219,7 +1219,7 @@ extern "C" int fv3_c_sw(fv3_ctx *c, const fv3_field *delp_, const fv3_field *pt_
   return fv3_post(c, s, "c_sw");
 }
 
-// the join c_sw left to the sequencer (seq_csw_defer): the caller's stream waits for the stage D / E windows on the auxiliary stream
+// the join c_sw left to the sequencer (seq.csw_defer): the caller's stream waits for the stage D / E windows on the auxiliary stream
 int fv3_csw_join(fv3_ctx *c, void *stream) {
   if (c && c->csw_pending) {
     fv3_wait(c, (fv3_stream_t)stream, 7);

@@ -160,7 +160,7 @@ FV3_HD inline bool fxadv_int_v(const Geo &g, int fl, int i, int j) {
 void fxadv(fv3_ctx *c, fv3_stream_t s, const Real *uc, const Real *vc, Real *crx, Real *cry, Real *xfx, Real *yfx, Real *ut, Real *vt, Real dt, Real *cx,
            Real *cy, bool thin_ut) {
   const Geo g = c->g;
-  const bool first = c->seq_acc_first;  // (the sequencer's first sub-step of a call: cx / cy hold nothing yet -- 0 + cr, the field is not read)
+  const bool first = c->seq.acc_first;  // (the sequencer's first sub-step of a call: cx / cy hold nothing yet -- 0 + cr, the field is not read)
   static const bool full_ut = fv3_sw(FV3SW_FXADV_FULL_UT);  // A/B switch
   if (full_ut) thin_ut = false;
   const int isd = 1 - g.nh, ied = g.nx + g.nh, jsd = 1 - g.nh, jed = g.ny + g.nh;
@@ -890,7 +890,7 @@ static void divdamp_patches(fv3_ctx *c, fv3_stream_t s, const Real *divgd, Real 
   }
 }
 
-// Does d_sw take the accumulators' first-sub-step form (fv3_ctx::seq_acc_first) in this configuration?  (the fused scalar marches and fxadv do; the
+// Does d_sw take the accumulators' first-sub-step form (fv3_seq_hints::acc_first) in this configuration?  (the fused scalar marches and fxadv do; the
 // round-1 "separate" transports accumulate through tp2d's epilogue and do not) -- fv3_acoustic_step asks before it leaves out the four zero launches.
 bool dsw_honors_acc_first(const fv3_ctx *c) {
   int nmax = 0;
@@ -935,7 +935,7 @@ static int acc_sum(fv3_ctx *c, Real *cx, Real *cy, int n, void *stream) {
   return fv3_post(c, (fv3_stream_t)stream, "acc_sum");
 }
 
-// Can d_sw leave cx / cy alone and keep the sub-step's Courant numbers in arrays of their own (fv3_ctx::seq_acc_defer)?  fxadv stores them exactly where it
+// Can d_sw leave cx / cy alone and keep the sub-step's Courant numbers in arrays of their own (fv3_seq_hints::acc_defer)?  fxadv stores them exactly where it
 // accumulates them; the round-1 ("separate") scalar form does not go through it with the sequencer's flags.
 bool dsw_can_defer_acc(const fv3_ctx *c) { return dsw_honors_acc_first(c); }
 
@@ -995,10 +995,10 @@ int fv3_d_sw_out(fv3_ctx *c, const fv3_field *delpc_, const fv3_field *delp_, co
   // FV3_DSW_SCALARS=separate: the four transports as four launches + the division kernel (round-1 form, A/B reference)
   const int sc_env = fv3_sw(FV3SW_DSW_SCALARS);  // (0 default, 1 separate, 2 quad; read per call: the A/B parity test flips it in one process)
   const bool fused_scalars = sc_env != 1 && nord_max_v <= 2 && nord_max_t <= 2 && nord_max_w <= 2;
-  if (c->seq_acc_first && !fused_scalars) return fv3_fail(c, FV3_ERR_ARG, "d_sw: the sequencer's first-sub-step form of the accumulators needs the fused scalar marches");
+  if (c->seq.acc_first && !fused_scalars) return fv3_fail(c, FV3_ERR_ARG, "d_sw: the sequencer's first-sub-step form of the accumulators needs the fused scalar marches");
   const int scalars_mode = sc_env == 2 ? 0 : 1;
   // deferred accumulation of the Courant numbers (fv3_step.hip): cx / cy are not touched by fxadv; crx / cry are this sub-step's own arrays (the sequencer hands them in)
-  const bool acc_defer = c->seq_acc_defer;
+  const bool acc_defer = c->seq.acc_defer;
   if (acc_defer && !fused_scalars) return fv3_fail(c, FV3_ERR_ARG, "d_sw: the sequencer's deferred accumulation needs the fused scalar marches (fxadv with the Courant numbers)");
   if (fused_scalars) {
     // ---- air mass, vertical velocity, condensate, potential temperature: the four del-n chains (bandwidth-bound, the
@@ -1039,7 +1039,7 @@ int fv3_d_sw_out(fv3_ctx *c, const fv3_field *delpc_, const fv3_field *delp_, co
     fv3_wait(c, s, 1);
     DswScalars q4{delp, w, q_con, pt, n_dp, n_w, n_qc, n_pt, heat_s, crx, cry, xfx, yfx, mfx, mfy, gx, gy, dA_x, dA_y, dQ_x, dQ_y, dB_x, dB_y, dC_x, dC_y,
                   cf.hord_dp, cf.hord_vt, cf.hord_tm, dn_vt, dn_t, dt, dn_w, fd_k0};
-    q4.acc_first = c->seq_acc_first;
+    q4.acc_first = c->seq.acc_first;
     q4.zeros = c->zeros;
     dsw_scalars_stream(c, s, q4, scalars_mode);
     if (!oop) launch3<4>(c, s, Box{1, g.nx, 1, g.ny, 0, nz1}, [=] FV3_HD(int t, int k, int i, int j) {
@@ -1371,9 +1371,9 @@ int fv3_d_sw_out(fv3_ctx *c, const fv3_field *delpc_, const fv3_field *delp_, co
   {
     const Real dddmp = (Real)cf.dddmp;
     // The operator's contract leaves the iterated divergence in divgd (D_SW-Out carries it).  Inside fv3_acoustic_step nobody reads it: the
-    // next c_sw overwrites the workspace field -- the sequencer says so (seq_divgd_dead) and the copy of the iteration's result into divgd
+    // next c_sw overwrites the workspace field -- the sequencer says so (seq.divgd_dead) and the copy of the iteration's result into divgd
     // (one field write per call) is skipped when the iteration wrote beside it.
-    const bool keep_divgd = !(c->seq_divgd_dead && dd_sep);
+    const bool keep_divgd = !(c->seq.divgd_dead && dd_sep);
     if (ks1 >= 0) a2b_ord4_t<8>(c, ss, wk, 0, 0, ks1 + 1, (Real)1, [=] FV3_HD(int t, int k, unsigned p, Real wkbv) {
       const int nord = g.nord[k];
       if (nord == 0) return;
@@ -1383,7 +1383,7 @@ int fv3_d_sw_out(fv3_ctx *c, const fv3_field *delpc_, const fv3_field *delp_, co
       if (dddmp >= (Real)1.0e-5) vo = fabs(dt) * sqrt(dpc * dpc + wkbv * wkbv);
       const Real damp2 = g.da_min_c * fv3_max(g.d2_divg[k], fv3_min((Real)0.20, dddmp * vo));
       const Real dn_ = (dnew + b)[p];
-      if (keep_divgd) (divgd + b)[p] = dn_;  // (no-op for the in-place staged form; skipped inside the sequencer: see seq_divgd_dead)
+      if (keep_divgd) (divgd + b)[p] = dn_;  // (no-op for the in-place staged form; skipped inside the sequencer: see seq.divgd_dead)
       const Real vd = damp2 * dpc + tab.dd8[k] * dn_;
       (vdamp + b)[p] = vd;
       (ke + b)[p] += vd;
@@ -1514,7 +1514,7 @@ int fv3_d_sw_out(fv3_ctx *c, const fv3_field *delpc_, const fv3_field *delp_, co
     // Round 5: on these levels the damping heat is the epilogue of the march (fv3_tp2x.hip, HEAT): the pre-damping winds and the two damping
     // increments are not stored and the damping-heat kernel below only serves the levels under fdw_k0.  FV3_DSW_HEAT=separate: the round-4
     // sequence (A/B; read per call).
-    TpHeat th{vdamp, o_delp, heat_s, g.d_con, heat_source, c->seq_heat_first ? c->zeros : nullptr};
+    TpHeat th{vdamp, o_delp, heat_s, g.d_con, heat_source, c->seq.heat_first ? c->zeros : nullptr};
     th.side_from = side_from;
     if (heat_in_march) e.heat = &th;
     tp2d(c, s, wk, crx, cry, xfx, yfx, fx, fy, nullptr, nullptr, nullptr, cf.hord_vt, nullptr, fdw_k0, nz1, &e);
@@ -1524,7 +1524,7 @@ int fv3_d_sw_out(fv3_ctx *c, const fv3_field *delpc_, const fv3_field *delp_, co
   }
 
   const bool heat_on = cf.d_con > 1.0e-5;
-  const bool heat_first = c->seq_heat_first;  // (the sequencer's first sub-step of a call: heat_source holds nothing yet -- 0 + heat, the field is not read)
+  const bool heat_first = c->seq.heat_first;  // (the sequencer's first sub-step of a call: heat_source holds nothing yet -- 0 + heat, the field is not read)
   // (two levels per thread: the six metric terms are read once)
   if (heat_k1 >= 0) launch3(c, s, Box{1, g.nx, 1, g.ny, 0, (heat_k1 + FV3_KC) / FV3_KC - 1}, [=] FV3_HD(int t, int kp, int i, int j) {
     const long m2 = t * g.st2;
@@ -1555,8 +1555,8 @@ int fv3_d_sw_out(fv3_ctx *c, const fv3_field *delpc_, const fv3_field *delp_, co
     }
   });
   // (deferred accumulation: the last d_sw of an acoustic call forms cx / cy from the sub-steps' Courant numbers)
-  if (acc_defer && c->seq_acc_sum_n > 0) {
-    const int st_ = acc_sum(c, cx, cy, c->seq_acc_sum_n, s);
+  if (acc_defer && c->seq.acc_sum_n > 0) {
+    const int st_ = acc_sum(c, cx, cy, c->seq.acc_sum_n, s);
     if (st_ != FV3_OK) return st_;
   }
   return fv3_post(c, s, "d_sw");

@@ -778,14 +778,14 @@ extern "C" int fv3_riem_solver3(fv3_ctx *c, int last_call, double dtd, const fv3
     // Frame-first passes of the sequencer (a transport is present): the columns are numbered frame first (ColumnOrder), pass 1 solves
     // the waves that hold frame columns, the halo updates of zh / pkc start, pass 2 solves the rest beside them.  Columns are
     // independent: the same values in any order.
-    const ColumnOrder ord{g.nx, g.ny, c->frame_pass != 0 ? FV3_FRAME_W : 0};
+    const ColumnOrder ord{g.nx, g.ny, c->seq.frame_pass != 0 ? FV3_FRAME_W : 0};
     const int nwave = (ncol + FV3_WAVE - 1) / FV3_WAVE;
-    const int nwave_frame = c->frame_pass != 0 ? (ord.n_frame() + FV3_WAVE - 1) / FV3_WAVE : 0;
-    const int w_lo = c->frame_pass == 2 ? nwave_frame : 0, w_hi = c->frame_pass == 1 ? nwave_frame : nwave;  // waves [w_lo, w_hi)
-    Real *const zn = c->dz_scan_src;  // (update_dz_d left its scan to this call: see fv3_ctx::seq_dz_scan)
+    const int nwave_frame = c->seq.frame_pass != 0 ? (ord.n_frame() + FV3_WAVE - 1) / FV3_WAVE : 0;
+    const int w_lo = c->seq.frame_pass == 2 ? nwave_frame : 0, w_hi = c->seq.frame_pass == 1 ? nwave_frame : nwave;  // waves [w_lo, w_hi)
+    Real *const zn = c->dz_scan_src;  // (update_dz_d left its scan to this call: see fv3_seq_hints::dz_scan)
     // Round 6: inside the sequencer only the LAST sub-step of an acoustic call stores the layer thickness -- the sub-steps between work from zh, and what reads delz
     // (the heights of the next call, the diffusive heating, the remap) comes after the last one: one field write less in five of six sub-steps.  FV3_SEQ_DELZ=every: A/B.
-    const bool store_delz = !(c->seq_delz_dead && !fv3_sw_is(FV3SW_SEQ_DELZ, "every"));
+    const bool store_delz = !(c->seq.delz_dead && !fv3_sw_is(FV3SW_SEQ_DELZ, "every"));
     const bool pre = zn != nullptr;
     const Real dzm = c->dz_scan_min;
     auto go_ = [&](auto last_tag, auto ra_tag, auto pre_tag) {
@@ -879,7 +879,7 @@ extern "C" int fv3_riem_solver3(fv3_ctx *c, int last_call, double dtd, const fv3
         go_(std::true_type{}, std::true_type{}, std::true_type{});
       else
         go_(std::false_type{}, std::true_type{}, std::true_type{});
-      if (c->frame_pass != 1) c->dz_scan_src = nullptr;  // (frame-first passes: both take the pre-sweep, each on its own columns)
+      if (c->seq.frame_pass != 1) c->dz_scan_src = nullptr;  // (frame-first passes: both take the pre-sweep, each on its own columns)
     } else if (last && ra)
       go_(std::true_type{}, std::true_type{}, std::false_type{});
     else if (last)
@@ -890,7 +890,7 @@ extern "C" int fv3_riem_solver3(fv3_ctx *c, int last_call, double dtd, const fv3
       go_(std::false_type{}, std::false_type{}, std::false_type{});
     return fv3_post(c, s, "riem_solver3");
   }
-  launch2_pass(c, s, Box{1, g.nx, 1, g.ny, 0, 0}, c->frame_pass, [=] FV3_HD(int t, int i, int j) {
+  launch2_pass(c, s, Box{1, g.nx, 1, g.ny, 0, 0}, c->seq.frame_pass, [=] FV3_HD(int t, int i, int j) {
     const long tb = t * g.st;
     const unsigned pix = IX(i, j);
     const long p = tb + pix;
@@ -948,7 +948,7 @@ extern "C" int fv3_p_grad_c(fv3_ctx *c, const fv3_field *uc_, const fv3_field *v
   // registers for the next level: every interface plane is read once instead of twice (9 -> 7 field passes).
   // (rolled loop: an unrolled level loop lets the compiler hoist every level's loads at once)
   const int nz = g.nz, nchunk = (nz + PG_KC - 1) / PG_KC;
-  launch3_pass(c, (fv3_stream_t)stream, Box{1, g.nx + 1, 1, g.ny + 1, 0, nchunk - 1}, c->frame_pass, [=] FV3_HD(int t, int kc, int i, int j) {
+  launch3_pass(c, (fv3_stream_t)stream, Box{1, g.nx + 1, 1, g.ny + 1, 0, nchunk - 1}, c->seq.frame_pass, [=] FV3_HD(int t, int kc, int i, int j) {
     const long m2 = t * g.st2;
     const unsigned p = IX(i, j), px = IX(i - 1, j), py = IX(i, j - 1);
     const bool do_u = j <= g.ny, do_v = i <= g.nx;
@@ -999,11 +999,11 @@ int fv3_nh_p_grad_scaled(fv3_ctx *c, const fv3_field *u_, const fv3_field *v_, c
   // product form: the four corner interpolations and the wind update as one marching kernel (fv3_pgf.hip); FV3_NH_PGF=staged keeps
   // the four a2b_ord4 launches + the level-walking update below (A/B reference)
   if (!fv3_sw_is(FV3SW_NH_PGF, "staged")) {  // (read per call: the A/B parity test flips it in one process)
-    nh_pgf_fused(c, s, pp, pk3, gz, delp, u, v, dt, top, (Real)gz_scale, c->frame_pass);
+    nh_pgf_fused(c, s, pp, pk3, gz, delp, u, v, dt, top, (Real)gz_scale, c->seq.frame_pass);
     return fv3_post(c, s, "nh_p_grad");
   }
   Real *ppb = c->scratch[SC_B], *pk3b = c->scratch[SC_C], *gzb = c->scratch[SC_D], *wk1 = c->scratch[SC_A];
-  if (c->frame_pass != 2) {  // (interior pass of the frame-first form: the corner fields are in scratch already)
+  if (c->seq.frame_pass != 2) {  // (interior pass of the frame-first form: the corner fields are in scratch already)
     launch2(c, s, Box{1, g.nx + 1, 1, g.ny + 1, 0, 0}, [=] FV3_HD(int t, int i, int j) {
       const long p = t * g.st + IX(i, j);
       ppb[p] = (Real)0;
@@ -1017,7 +1017,7 @@ int fv3_nh_p_grad_scaled(fv3_ctx *c, const fv3_field *u_, const fv3_field *v_, c
   // A thread walks PG_KC levels keeping the lower-interface corner values (pk3, gz, pp at k+1, three corners each)
   // in registers for the next level: every interface plane is read once instead of twice (11 -> 8 field passes).
   const int nchunk = (nz + PG_KC - 1) / PG_KC;
-  launch3_pass(c, s, Box{1, g.nx + 1, 1, g.ny + 1, 0, nchunk - 1}, c->frame_pass, [=] FV3_HD(int t, int kc, int i, int j) {
+  launch3_pass(c, s, Box{1, g.nx + 1, 1, g.ny + 1, 0, nchunk - 1}, c->seq.frame_pass, [=] FV3_HD(int t, int kc, int i, int j) {
     const long m2 = t * g.st2;
     const unsigned p = IX(i, j), pe_ = IX(i + 1, j), pn = IX(i, j + 1);
     const bool do_u = i <= g.nx, do_v = j <= g.ny;
@@ -1430,9 +1430,9 @@ extern "C" int fv3_update_dz_d(fv3_ctx *c, const fv3_field *zs_, const fv3_field
     del6_vt_flux_patches(c, s, zh, d2, fx2, fy2, dn, false, fd_k0, nz);
   else
     del6_vt_flux_edge_strips(c, s, zh, d2, fx2, fy2, dn, false, fd_k0, nz);
-  // Round 6: inside the sequencer (fv3_ctx::seq_dz_scan) the scan at the end of this operator becomes the pre-sweep of riem_solver3's wave form, which reads the
+  // Round 6: inside the sequencer (fv3_seq_hints::dz_scan) the scan at the end of this operator becomes the pre-sweep of riem_solver3's wave form, which reads the
   // marched heights where this call leaves them (the free slot SC_F: riem_solver3's scratch fields are SC_A / C / D / E).  FV3_DZ_SCAN=separate: the kernel below (A/B).
-  const bool scan_deferred = c->seq_dz_scan && riem_wave_ok(g, true) && riem_reg_arrays(g) && !fv3_sw_is(FV3SW_DZ_SCAN, "separate");
+  const bool scan_deferred = c->seq.dz_scan && riem_wave_ok(g, true) && riem_reg_arrays(g) && !fv3_sw_is(FV3SW_DZ_SCAN, "separate");
   Real *znew = scan_deferred ? fy : fx;
   {
     TpEpi e{znew, nullptr, false, nullptr, nullptr, nullptr, nullptr, nullptr, true, fx2, fy2, g.damp_vt, nullptr, nullptr};
@@ -1508,7 +1508,7 @@ extern "C" int fv3_ray_fast(fv3_ctx *c, const fv3_field *u_, const fv3_field *v_
   const Real dm = (Real)c->rf_dm;
   const Real *rf = (const Real *)c->tab_rf;
   const bool momentum_fix = !fv3_alt("ray_fast_plain");  // (FV3_ALT: DESIGN §2, uncertain restatement 4)
-  launch2_pass(c, (fv3_stream_t)stream, Box{1, g.nx + 1, 1, g.ny + 1, 0, 0}, c->frame_pass, [=] FV3_HD(int t, int i, int j) {
+  launch2_pass(c, (fv3_stream_t)stream, Box{1, g.nx + 1, 1, g.ny + 1, 0, 0}, c->seq.frame_pass, [=] FV3_HD(int t, int i, int j) {
     const long tb = t * g.st;
     const unsigned pix = IX(i, j);
     const long p = tb + pix;

@@ -116,7 +116,7 @@ struct DswScalars {
   Real dt;
   Deln dn_w;  // w's chain (fused form: the march runs it; the other forms only test its switch through g.damp_w)
   int fd_k0;  // levels >= fd_k0 run the del-n chains inside the marches (every chain of order 2 there); nz = never
-  // first sub-step of an acoustic call inside the sequencer (fv3_ctx::seq_acc_first): mfx / mfy hold nothing yet -- the marches add the flux to a zero
+  // first sub-step of an acoustic call inside the sequencer (fv3_seq_hints::acc_first): mfx / mfy hold nothing yet -- the marches add the flux to a zero
   // read from `zeros` (one level plane, read with the field's own in-plane offsets; it stays in L2) instead of reading the fields
   bool acc_first = false;
   const Real *zeros = nullptr;
@@ -195,7 +195,7 @@ int fv3_d_sw_out(fv3_ctx *c, const fv3_field *delpc, const fv3_field *delp, cons
                  const fv3_field *yfx, const fv3_field *q_con, const fv3_field *zh, const fv3_field *heat_source, const fv3_field *diss_est, double dt,
                  void *stream, const fv3_field *o_delp, const fv3_field *o_pt, const fv3_field *o_w, const fv3_field *o_q_con, int (*after_scalars)(void *) = nullptr,
                  void *after_user = nullptr);  // after_scalars: called once the four new scalars are final (the winds still to come)
-int fv3_csw_join(fv3_ctx *c, void *stream);  // (fv3_csw.hip) the join of c_sw's deferred stage D / E windows (fv3_ctx::seq_csw_defer)
+int fv3_csw_join(fv3_ctx *c, void *stream);  // (fv3_csw.hip) the join of c_sw's deferred stage D / E windows (fv3_seq_hints::csw_defer)
 // nh_p_grad as one marching kernel (fv3_pgf.hip); pass = the sequencer's frame-first pass (0 all, 1 sub-domain frames, 2 the rest)
 void nh_pgf_fused(fv3_ctx *c, fv3_stream_t s, const Real *pp, const Real *pk3, const Real *gz, const Real *delp, Real *u, Real *v, Real dt, Real top, Real gz_scale,
                   int pass);

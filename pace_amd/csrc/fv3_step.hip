@@ -74,6 +74,28 @@ int copy_part(fv3_ctx *c, const fv3_field *src, const fv3_field *dst, int part, 
   return fv3_post(c, s, "copy_part");
 }
 
+// The frame of a plane -- every cell outside the compute cells -- as one index range: the row bands below and above the compute rows at full width
+// first, then the column bands beside the compute rows.  copy_frames and zero_unwritten run a thread per frame cell and level over it.
+// Frame cell idx -> (i, j); false: idx is past the frame.
+FV3_HD inline bool frame_cell(const Geo &g, int idx, int &i, int &j) {
+  const int ia = -g.o, ja = -g.o;
+  const int nlo = 1 - ja, nhi = g.nj - 1 - g.o - g.ny;  // rows below / above the compute rows
+  const int wlo = 1 - ia, whi = g.ni - 1 - g.o - g.nx;  // columns left / right of the compute columns
+  const int n_rows = (nlo + nhi) * g.ni, w = wlo + whi;
+  if (idx >= n_rows + w * g.ny) return false;
+  if (idx < n_rows) {  // the row bands: full width
+    const int r = idx / g.ni;
+    i = ia + (idx - r * g.ni);
+    j = r < nlo ? ja + r : g.ny + 1 + (r - nlo);
+  } else {  // the column bands beside the compute rows
+    const int m = idx - n_rows, r = m / w, cidx = m - r * w;
+    j = 1 + r;
+    i = cidx < wlo ? ia + cidx : g.nx + 1 + (cidx - wlo);
+  }
+  return true;
+}
+inline int frame_cells(const Geo &g) { return g.ni * g.nj - g.nx * g.ny; }
+
 // copy_part(.., 2) of up to four fields in ONE launch, a thread per frame cell and level (the frame = every plane cell outside the compute
 // cells: 4 x 391 + ... of 391^2 at C768 layout 2 x 2).  As four launches per field -- row bands 64 lanes wide, column bands with 4 of 64 lanes
 // active -- the sixteen launches of a call took 3.2 ms for 90 MB; this one takes what its bytes cost.
@@ -88,24 +110,10 @@ int copy_frames(fv3_ctx *c, int n, const fv3_field *const *src, const fv3_field 
   const Real *a0 = a[0], *a1 = a[1], *a2 = a[2], *a3 = a[3];
   Real *b0 = b[0], *b1 = b[1], *b2 = b[2], *b3 = b[3];
   const Geo g = c->g;
-  const int ia = -g.o, ja = -g.o;
-  const int nlo = 1 - ja, nhi = g.nj - 1 - g.o - g.ny;     // rows below / above the compute rows
-  const int wlo = 1 - ia, whi = g.ni - 1 - g.o - g.nx;     // columns left / right of the compute columns
-  const int n_rows = (nlo + nhi) * g.ni, n_cols = (wlo + whi) * g.ny, n_frame = n_rows + n_cols;
-  const int W = (n_frame + 3) / 4;
+  const int W = (frame_cells(g) + 3) / 4;
   launch3<4>(c, (fv3_stream_t)stream, Box{1, W, 1, 4, 0, g.nz - 1}, [=] FV3_HD(int t, int k, int ii, int jj) {
-    const int idx = (jj - 1) * W + (ii - 1);
-    if (idx >= n_frame) return;
     int i, j;
-    if (idx < n_rows) {  // the row bands: full width
-      const int r = idx / g.ni;
-      i = ia + (idx - r * g.ni);
-      j = r < nlo ? ja + r : g.ny + 1 + (r - nlo);
-    } else {  // the column bands beside the compute rows
-      const int m = idx - n_rows, w = wlo + whi, r = m / w, cidx = m - r * w;
-      j = 1 + r;
-      i = cidx < wlo ? ia + cidx : g.nx + 1 + (cidx - wlo);
-    }
+    if (!frame_cell(g, (jj - 1) * W + (ii - 1), i, j)) return;
     const long p = t * g.st + k * g.sk + IX(i, j);
     b0[p] = a0[p];
     if (b1) b1[p] = a1[p];
@@ -115,7 +123,7 @@ int copy_frames(fv3_ctx *c, int n, const fv3_field *const *src, const fv3_field 
   return fv3_post(c, (fv3_stream_t)stream, "copy_frames");
 }
 
-// What the first-sub-step form of the accumulators (fv3_ctx::seq_acc_first / seq_heat_first) leaves to the sequencer: the first d_sw of a call STORES 0 + flux on
+// What the first-sub-step form of the accumulators (fv3_seq_hints::acc_first / heat_first) leaves to the sequencer: the first d_sw of a call STORES 0 + flux on
 // every face / cell it owns, so the only cells of mfx / mfy / cx / cy / heat_source that still need the reference's zero_data are the ones d_sw never writes -- the
 // frame of every plane outside the operator's write set and the padding level nz.  They are zeroed here on EVERY call (a thread per frame cell and level, as
 // copy_frames; ~4 % of a field for the five of them together), so the result does not depend on what the arrays held before the call: no "zeroed once" flag keyed on a
@@ -135,25 +143,11 @@ int zero_unwritten(fv3_ctx *c, const fv3_field *mfx_, const fv3_field *mfy_, con
   if (!any) return FV3_OK;
   Real *mfx = f[0], *mfy = f[1], *cx = f[2], *cy = f[3], *heat = f[4];
   const Geo g = c->g;
-  const int ia = -g.o, ja = -g.o;
-  const int nlo = 1 - ja, nhi = g.nj - 1 - g.o - g.ny;  // rows below / above the compute rows
-  const int wlo = 1 - ia, whi = g.ni - 1 - g.o - g.nx;  // columns left / right of the compute columns
-  const int n_rows = (nlo + nhi) * g.ni, n_cols = (wlo + whi) * g.ny, n_frame = n_rows + n_cols;
-  const int W = (n_frame + 3) / 4;
+  const int W = (frame_cells(g) + 3) / 4;
   const int isd = 1 - g.nh, ied = g.nx + g.nh, jsd = 1 - g.nh, jed = g.ny + g.nh;
   launch3<4>(c, (fv3_stream_t)stream, Box{1, W, 1, 4, 0, g.nz - 1}, [=] FV3_HD(int t, int k, int ii, int jj) {
-    const int idx = (jj - 1) * W + (ii - 1);
-    if (idx >= n_frame) return;
     int i, j;
-    if (idx < n_rows) {  // the row bands: full width
-      const int r = idx / g.ni;
-      i = ia + (idx - r * g.ni);
-      j = r < nlo ? ja + r : g.ny + 1 + (r - nlo);
-    } else {  // the column bands beside the compute rows
-      const int m = idx - n_rows, w = wlo + whi, r = m / w, cidx = m - r * w;
-      j = 1 + r;
-      i = cidx < wlo ? ia + cidx : g.nx + 1 + (cidx - wlo);
-    }
+    if (!frame_cell(g, (jj - 1) * W + (ii - 1), i, j)) return;
     const long p = t * g.st + k * g.sk + IX(i, j);
     const bool xf = i >= 1 && i <= g.nx + 1, yf = j >= 1 && j <= g.ny + 1;  // on an owned x face column / y face row
     const bool xc = i >= 1 && i <= g.nx, yc = j >= 1 && j <= g.ny;
@@ -163,7 +157,7 @@ int zero_unwritten(fv3_ctx *c, const fv3_field *mfx_, const fv3_field *mfy_, con
     if (cy && !(yf && i >= isd && i <= ied)) cy[p] = (Real)0;
     if (heat) heat[p] = (Real)0;  // (every frame cell lies outside [1, nx] x [1, ny])
   });
-  launch3<4>(c, (fv3_stream_t)stream, Box{ia, g.ni - 1 - g.o, ja, g.nj - 1 - g.o, g.nz, g.nz}, [=] FV3_HD(int t, int k, int i, int j) {
+  launch3<4>(c, (fv3_stream_t)stream, Box{-g.o, g.ni - 1 - g.o, -g.o, g.nj - 1 - g.o, g.nz, g.nz}, [=] FV3_HD(int t, int k, int i, int j) {
     const long p = t * g.st + k * g.sk + IX(i, j);
     if (mfx) mfx[p] = (Real)0;
     if (mfy) mfy[p] = (Real)0;
@@ -217,11 +211,28 @@ extern "C" int fv3_profile_read(fv3_ctx *c, double *ms_sum, int64_t *calls, int 
   return FV3_OK;
 }
 
+// The hints of ONE operator call (fv3_ctx::seq): installed here, the defaults back when the scope ends -- whichever way the call ends.
+struct SeqScope {
+  fv3_ctx *c;
+  SeqScope(fv3_ctx *c_, const fv3_seq_hints &h) : c(c_) { c->seq = h; }
+  ~SeqScope() { c->seq = fv3_seq_hints{}; }
+};
+// ... the same for OpTimer's parent: what is timed inside the scope is taken out of that operator's own time
+struct ProfParentScope {
+  fv3_ctx *c;
+  ProfParentScope(fv3_ctx *c_, int op) : c(c_) { c->prof_parent = op; }
+  ~ProfParentScope() { c->prof_parent = -1; }
+};
+
+#define TRY(call)                       \
+  do {                                  \
+    const int st_ = (call);             \
+    if (st_ != FV3_OK) return st_;      \
+  } while (0)
 #define RUN(op, call)                   \
   do {                                  \
     OpTimer tm_(c, s, op);              \
-    const int st_ = (call);             \
-    if (st_ != FV3_OK) return st_;      \
+    TRY(call);                          \
   } while (0)
 #define HALO(id, phase)                                                                                  \
   do {                                                                                                   \
@@ -230,6 +241,15 @@ extern "C" int fv3_profile_read(fv3_ctx *c, double *ms_sum, int64_t *calls, int 
     if (st_ != 0) return halo ? fv3_fail(c, FV3_ERR_ARG, "acoustic_step: the halo callback reported an error") : st_; \
   } while (0)
 
+// What the sequencer tells the operators (fv3_seq_hints, one SeqScope per call; an operator called from anywhere else sees the defaults):
+//   hint                     set for                                          read by                        A/B switch
+//   csw_defer, uava_thin     c_sw (uava_thin: all but the last)               fv3_csw.hip                    FV3_CSW_DEFER=1 (off without), FV3_SEQ_UAVA=every
+//   frame_pass 1, 2          p_grad_c, riem_solver3, nh_p_grad + ray_fast     fv3_nh.hip                     FV3_FRAME_FIRST=0 / 1
+//   divgd_dead               d_sw, with the ping-pong                         fv3_dsw.hip                    FV3_SEQ_KEEP_DIVGD=1
+//   acc_first, heat_first    d_sw of the first sub-step                       fv3_dsw.hip                    FV3_ACC_STORE=0
+//   acc_defer, acc_sum_n     d_sw (acc_sum_n: the last)                       fv3_dsw.hip                    FV3_ACC_DEFER=0
+//   dz_scan                  update_dz_d                                      fv3_nh.hip                     FV3_DZ_SCAN=separate
+//   delz_dead                riem_solver3, all but the last                   fv3_nh.hip                     FV3_SEQ_DELZ=every
 extern "C" int fv3_acoustic_step(fv3_ctx *c, const fv3_state *st, const fv3_workspace *ws, double timestep, int n_map, fv3_halo_fn halo, void *halo_user,
                                  void *stream) {
   if (!c || !st || !ws) return FV3_ERR_ARG;
@@ -270,26 +290,29 @@ extern "C" int fv3_acoustic_step(fv3_ctx *c, const fv3_state *st, const fv3_work
   bool frame_first = !halo && (c->nccl_comm != nullptr || c->xfer != nullptr);
   if (const int e = fv3_sw(FV3SW_FRAME_FIRST); e >= 0) frame_first = !halo && e == 1;
   bool w_started = false;
-  c->frame_pass = 0;
-  struct PpGuard {  // (no early return leaves the halo translation switched on, or c_sw's deferred windows unjoined)
+  struct PpGuard {  // (no early return leaves the halo translation switched on, c_sw's deferred windows unjoined or update_dz_d's scan owed)
     fv3_ctx *c;
     void *stream;
     ~PpGuard() {
       (void)fv3_csw_join(c, stream);
       c->pp_n = 0;
-      c->frame_pass = 0;
-      c->seq_divgd_dead = false;
-      c->seq_acc_first = false;
-      c->seq_heat_first = false;
-      c->seq_csw_defer = false;
-      c->seq_dz_scan = false;
-      c->seq_delz_dead = false;
-      c->seq_uava_thin = false;
-      c->seq_acc_defer = false;
-      c->seq_acc_sum_n = 0;
       c->dz_scan_src = nullptr;
+      c->seq = {};  // (backstop: every SeqScope has put the defaults back already)
     }
   } pp_guard{c, stream};
+  // An operator that feeds halo updates.  Frame-first: op on the frame of every sub-domain, the updates start, op on the interior beside the messages;
+  // otherwise op on the whole box, then the start.  op(hints) and start() return a status.
+  auto feed_halos = [&](fv3_seq_hints h, auto &&op, auto &&start) -> int {
+    if (frame_first) {
+      h.frame_pass = 1;
+      TRY(op(h));
+      TRY(start());
+      h.frame_pass = 2;
+      return op(h);
+    }
+    TRY(op(h));
+    return start();
+  };
 
   if (pingpong) {
     // cells no operator and no halo update ever writes (the 3 x 3 blocks beyond a cube corner, the allocation padding) keep the
@@ -304,7 +327,7 @@ extern "C" int fv3_acoustic_step(fv3_ctx *c, const fv3_state *st, const fv3_work
   // "Empty the flux capacitors" (dyn_core.F90): the accumulated mass fluxes / Courant numbers cover ONE call -- the tracer
   // advection that follows each call consumes exactly them (dp2 = dp1 + div(mfx) must be the air mass after this call)
   (void)n_map;
-  // Round 5: the first sub-step's d_sw STORES 0 + flux instead of accumulating into zeroed fields (fv3_ctx::seq_acc_first: the zero is read from a one-plane
+  // Round 5: the first sub-step's d_sw STORES 0 + flux instead of accumulating into zeroed fields (fv3_seq_hints::acc_first: the zero is read from a one-plane
   // block, not from the field): four 2.3 GB zero launches and four field reads less per call.  Round 6: the cells d_sw never writes (frame of every plane, padding
   // level) are zeroed on every call by zero_unwritten -- whatever the arrays held before the call, every cell ends up with what zero + accumulate leaves there.
   // FV3_ACC_STORE=0: zero + accumulate on every sub-step (A/B; same bits: 0 + x is what the accumulation computes on a zeroed field).
@@ -342,14 +365,14 @@ extern "C" int fv3_acoustic_step(fv3_ctx *c, const fv3_state *st, const fv3_work
     }
     HALO(FV3_HALO_U__V, 1);
     HALO(FV3_HALO_W, 1);
-    // (its last window launches may still run on the auxiliary stream beside update_dz_c: joined before riem_solver_c.  Only beside the one-kernel zh -> gz form of
-    //  update_dz_c: the in-place form of the reference's first sub-step order works in the scratch field c_sw keeps its kinetic energy in)
-    c->seq_csw_defer = (gz_direct || it > 0) && c->g.nz >= 3;
-    c->seq_uava_thin = it < n_split - 1;  // (ua / va: outputs of the call -- the last sub-step's; before that only d_sw's divergence and c_sw's own windows read them: fv3_csw.hip, sua)
-    RUN(FV3_OP_C_SW, fv3_c_sw(c, &f_delp[cur], &f_pt[cur], &st->u, &st->v, &f_w[cur], &st->uc, &st->vc, &st->ua, &st->va, &ws->ut, &ws->vt, &ws->divgd, &st->omga,
-                              &ws->delpc, &ws->ptc, dt2, stream));
-    c->seq_csw_defer = false;
-    c->seq_uava_thin = false;
+    // (csw_defer: its last window launches may still run on the auxiliary stream beside update_dz_c: joined before riem_solver_c.  Only beside the one-kernel zh -> gz form of
+    //  update_dz_c: the in-place form of the reference's first sub-step order works in the scratch field c_sw keeps its kinetic energy in.
+    //  uava_thin: ua / va are outputs of the call -- the last sub-step's; before that only d_sw's divergence and c_sw's own windows read them: fv3_csw.hip, sua)
+    {
+      SeqScope seq_(c, {.csw_defer = (gz_direct || it > 0) && c->g.nz >= 3, .uava_thin = it < n_split - 1});
+      RUN(FV3_OP_C_SW, fv3_c_sw(c, &f_delp[cur], &f_pt[cur], &st->u, &st->v, &f_w[cur], &st->uc, &st->vc, &st->ua, &st->va, &ws->ut, &ws->vt, &ws->divgd, &st->omga,
+                                &ws->delpc, &ws->ptc, dt2, stream));
+    }
     if (cf.nord > 0) HALO(FV3_HALO_DIVGD, 0);
     if (it == 0 && gz_direct) {
       HALO(FV3_HALO_ZH, 1);
@@ -365,17 +388,15 @@ extern "C" int fv3_acoustic_step(fv3_ctx *c, const fv3_state *st, const fv3_work
     RUN(FV3_OP_GLUE, fv3_csw_join(c, stream));  // (what is left of c_sw's deferred windows when update_dz_c is done: timed as glue)
     RUN(FV3_OP_RIEM_SOLVER_C,
         fv3_riem_solver_c(c, dt2, &st->cappa, ptop, &st->phis, &ws->ws3, &ws->ptc, &f_qc[cur], &ws->delpc, &ws->gz, &ws->pkc, &st->omga, stream));
-    if (frame_first) {
-      c->frame_pass = 1;
+    auto p_grad_c = [&](const fv3_seq_hints &h) -> int {
+      SeqScope seq_(c, h);
       RUN(FV3_OP_P_GRAD_C, fv3_p_grad_c(c, &st->uc, &st->vc, &ws->delpc, &ws->pkc, &ws->gz, dt2, stream));
+      return FV3_OK;
+    };
+    TRY(feed_halos({}, p_grad_c, [&]() -> int {
       HALO(FV3_HALO_UC__VC, 0);
-      c->frame_pass = 2;
-      RUN(FV3_OP_P_GRAD_C, fv3_p_grad_c(c, &st->uc, &st->vc, &ws->delpc, &ws->pkc, &ws->gz, dt2, stream));
-      c->frame_pass = 0;
-    } else {
-      RUN(FV3_OP_P_GRAD_C, fv3_p_grad_c(c, &st->uc, &st->vc, &ws->delpc, &ws->pkc, &ws->gz, dt2, stream));
-      HALO(FV3_HALO_UC__VC, 0);
-    }
+      return FV3_OK;
+    }));
     if (cf.nord > 0) HALO(FV3_HALO_DIVGD, 1);
     HALO(FV3_HALO_UC__VC, 1);
     // (deferred accumulation: this sub-step's Courant numbers go to -- and are read from, by d_sw and update_dz_d -- arrays of its own)
@@ -383,111 +404,79 @@ extern "C" int fv3_acoustic_step(fv3_ctx *c, const fv3_state *st, const fv3_work
     if (acc_defer) {
       f_crx.ptr = c->acc_slots[2 * it];
       f_cry.ptr = c->acc_slots[2 * it + 1];
-      c->seq_acc_defer = true;
-      c->seq_acc_sum_n = it == n_split - 1 ? n_split : 0;  // (the last d_sw of the call ends with the sum of the sub-steps' arrays: fv3_dsw.hip, acc_sum)
     }
-    if (pingpong) {
-      // d_sw writes the new delp / pt / w / q_con into the other half of the pair.  Their halo update STARTS inside the operator, as
-      // soon as the scalar marches are done, and is waited for after it: with a communicator the exchange (communication stream)
-      // overlaps d_sw's whole wind part [REF docs/util/communication.rst:100-109,169-176: start() ... compute ... wait()]
-      const int nxt = 1 - cur;
-      struct Mid {
-        fv3_ctx *c;
-        int pp_n_next;
-        void *stream;
-        fv3_stream_t s;
-      } mid{c, nxt ? 4 : 0, stream, s};
-      auto start_halo = [](void *u) -> int {
-        Mid *m = (Mid *)u;
-        fv3_ctx *c = m->c;
-        fv3_stream_t s = m->s;
-        m->c->pp_n = m->pp_n_next;  // delp / pt / q_con now live in the half d_sw has just written
-        c->prof_parent = FV3_OP_D_SW;  // (timed as halo, not as d_sw)
-        int st_;
-        {
-          OpTimer tm_(c, s, FV3_OP_HALO);
-          st_ = fv3_halo_step(m->c, FV3_HALO_DELP__PT__Q_CON, 0, m->stream);
-        }
-        c->prof_parent = -1;
-        return st_;
-      };
-      c->seq_divgd_dead = !fv3_sw(FV3SW_SEQ_KEEP_DIVGD);
-      c->seq_acc_first = acc_store && it == 0;
-      c->seq_heat_first = heat_store && it == 0;
+    // With the ping-pong d_sw writes the new delp / pt / w / q_con into the other half of the pair.  Their halo update STARTS inside the operator, as
+    // soon as the scalar marches are done, and is waited for after it: with a communicator the exchange (communication stream)
+    // overlaps d_sw's whole wind part [REF docs/util/communication.rst:100-109,169-176: start() ... compute ... wait()]
+    const int nxt = pingpong ? 1 - cur : cur;
+    struct Mid {
+      fv3_ctx *c;
+      int pp_n_next;
+      void *stream;
+      fv3_stream_t s;
+    } mid{c, nxt ? 4 : 0, stream, s};
+    auto start_halo = [](void *u) -> int {
+      Mid *m = (Mid *)u;
+      m->c->pp_n = m->pp_n_next;  // delp / pt / q_con now live in the half d_sw has just written
+      ProfParentScope parent_(m->c, FV3_OP_D_SW);  // (timed as halo, not as d_sw)
+      OpTimer tm_(m->c, m->s, FV3_OP_HALO);
+      return fv3_halo_step(m->c, FV3_HALO_DELP__PT__Q_CON, 0, m->stream);
+    };
+    {
+      // (acc_sum_n: the last d_sw of the call ends with the sum of the sub-steps' arrays: fv3_dsw.hip, acc_sum)
+      SeqScope seq_(c, {.divgd_dead = pingpong && !fv3_sw(FV3SW_SEQ_KEEP_DIVGD), .acc_first = acc_store && it == 0, .heat_first = heat_store && it == 0,
+                        .acc_defer = acc_defer, .acc_sum_n = acc_defer && it == n_split - 1 ? n_split : 0});
       RUN(FV3_OP_D_SW, fv3_d_sw_out(c, &ws->dsw_delpc, &f_delp[cur], &f_pt[cur], &st->u, &st->v, &f_w[cur], &st->uc, &st->vc, &st->ua, &st->va, &ws->divgd, &st->mfxd,
                                     &st->mfyd, &st->cxd, &st->cyd, &f_crx, &f_cry, &ws->xfx, &ws->yfx, &f_qc[cur], &ws->zh, &ws->heat_source, &st->diss_estd, dt,
-                                    stream, &f_delp[nxt], &f_pt[nxt], &f_w[nxt], &f_qc[nxt], +start_halo, &mid));
-      c->seq_divgd_dead = false;
-      c->seq_acc_first = false;
-      c->seq_heat_first = false;
-      cur = nxt;
-      c->pp_n = cur ? 4 : 0;
-    } else {
-      c->seq_acc_first = acc_store && it == 0;
-      c->seq_heat_first = heat_store && it == 0;
-      RUN(FV3_OP_D_SW, fv3_d_sw(c, &ws->dsw_delpc, &f_delp[cur], &f_pt[cur], &st->u, &st->v, &f_w[cur], &st->uc, &st->vc, &st->ua, &st->va, &ws->divgd, &st->mfxd, &st->mfyd,
-                                &st->cxd, &st->cyd, &f_crx, &f_cry, &ws->xfx, &ws->yfx, &f_qc[cur], &ws->zh, &ws->heat_source, &st->diss_estd, dt, stream));
-      c->seq_acc_first = false;
-      c->seq_heat_first = false;
-      HALO(FV3_HALO_DELP__PT__Q_CON, 0);
+                                    stream, pingpong ? &f_delp[nxt] : nullptr, pingpong ? &f_pt[nxt] : nullptr, pingpong ? &f_w[nxt] : nullptr,
+                                    pingpong ? &f_qc[nxt] : nullptr, pingpong ? +start_halo : nullptr, &mid));
     }
-    c->seq_acc_defer = false;
-    c->seq_acc_sum_n = 0;
+    cur = nxt;
+    c->pp_n = cur ? 4 : 0;
+    if (!pingpong) HALO(FV3_HALO_DELP__PT__Q_CON, 0);  // (in place: the update starts behind the operator)
     HALO(FV3_HALO_DELP__PT__Q_CON, 1);
-    c->seq_dz_scan = true;  // (its closing scan becomes riem_solver3's pre-sweep: nothing between the two reads zh or wsd)
-    RUN(FV3_OP_UPDATE_DZ_D, fv3_update_dz_d(c, &ws->zs, &ws->zh, &f_crx, &f_cry, &ws->xfx, &ws->yfx, &ws->wsd, dt, stream));
-    c->seq_dz_scan = false;
-    c->seq_delz_dead = it < n_split - 1;  // (delz is read after the last sub-step of a call only: fv3_nh.hip, store_delz)
-    if (frame_first) {
-      // the frame columns of the new zh / pkc first, their updates start, the interior columns follow beside the messages
-      c->frame_pass = 1;
-      RUN(FV3_OP_RIEM_SOLVER3, fv3_riem_solver3(c, remap_step, dt, &st->cappa, ptop, &ws->zs, &ws->wsd, &st->delz, &f_qc[cur], &f_delp[cur], &f_pt[cur], &ws->zh, &st->pe,
-                                                &ws->pkc, &ws->pk3, &st->pk, &st->peln, &f_w[cur], stream));
-      HALO(FV3_HALO_ZH, 0);
-      HALO(FV3_HALO_PKC, 0);
-      c->frame_pass = 2;
-      RUN(FV3_OP_RIEM_SOLVER3, fv3_riem_solver3(c, remap_step, dt, &st->cappa, ptop, &ws->zs, &ws->wsd, &st->delz, &f_qc[cur], &f_delp[cur], &f_pt[cur], &ws->zh, &st->pe,
-                                                &ws->pkc, &ws->pk3, &st->pk, &st->peln, &f_w[cur], stream));
-      c->frame_pass = 0;
-    } else {
-      RUN(FV3_OP_RIEM_SOLVER3, fv3_riem_solver3(c, remap_step, dt, &st->cappa, ptop, &ws->zs, &ws->wsd, &st->delz, &f_qc[cur], &f_delp[cur], &f_pt[cur], &ws->zh, &st->pe,
-                                                &ws->pkc, &ws->pk3, &st->pk, &st->peln, &f_w[cur], stream));
-      HALO(FV3_HALO_ZH, 0);
-      HALO(FV3_HALO_PKC, 0);
+    {
+      SeqScope seq_(c, {.dz_scan = true});  // (its closing scan becomes riem_solver3's pre-sweep: nothing between the two reads zh or wsd)
+      RUN(FV3_OP_UPDATE_DZ_D, fv3_update_dz_d(c, &ws->zs, &ws->zh, &f_crx, &f_cry, &ws->xfx, &ws->yfx, &ws->wsd, dt, stream));
     }
-    c->seq_delz_dead = false;
+    // (frame-first: the frame columns of the new zh / pkc first, their updates start, the interior columns follow beside the messages)
+    auto riem_solver3 = [&](const fv3_seq_hints &h) -> int {
+      SeqScope seq_(c, h);
+      RUN(FV3_OP_RIEM_SOLVER3, fv3_riem_solver3(c, remap_step, dt, &st->cappa, ptop, &ws->zs, &ws->wsd, &st->delz, &f_qc[cur], &f_delp[cur], &f_pt[cur], &ws->zh, &st->pe,
+                                                &ws->pkc, &ws->pk3, &st->pk, &st->peln, &f_w[cur], stream));
+      return FV3_OK;
+    };
+    // (delz is read after the last sub-step of a call only: fv3_nh.hip, store_delz)
+    TRY(feed_halos({.delz_dead = it < n_split - 1}, riem_solver3, [&]() -> int {
+      HALO(FV3_HALO_ZH, 0);
+      HALO(FV3_HALO_PKC, 0);
+      return FV3_OK;
+    }));
     if (remap_step) RUN(FV3_OP_PK3_HALO, fv3_edge_pe(c, &st->pe, &f_delp[cur], ptop, stream));
     RUN(FV3_OP_PK3_HALO, fv3_pk3_halo(c, &ws->pk3, &f_delp[cur], ptop, akap, stream));
     HALO(FV3_HALO_ZH, 1);
     HALO(FV3_HALO_PKC, 1);
-    if (frame_first) {
-      // the frame of the new u / v / w first (pressure gradient + Rayleigh damping), the updates start, the interior follows
-      c->frame_pass = 1;
+    // (frame-first: the frame of the new u / v / w first -- pressure gradient + Rayleigh damping --, the updates start, the interior follows.
+    //  The reference stores gz = g * zh first -- compute_geopotential; here the corner interpolation reads zh and scales it)
+    auto nh_p_grad = [&](const fv3_seq_hints &h) -> int {
+      SeqScope seq_(c, h);
       RUN(FV3_OP_NH_P_GRAD, fv3_nh_p_grad_scaled(c, &st->u, &st->v, &ws->pkc, &ws->zh, &ws->pk3, &f_delp[cur], dt, ptop, akap, c->cst.grav, stream));
       if (cf.rf_fast) RUN(FV3_OP_RAY_FAST, fv3_ray_fast(c, &st->u, &st->v, &f_w[cur], dt, ptop, stream));
-      if (it != n_split - 1) {
-        HALO(FV3_HALO_U__V, 0);
-        HALO(FV3_HALO_W, 0);  // (w is final too: the next sub-step finds its update in flight)
-        w_started = true;
-      } else {
+      return FV3_OK;
+    };
+    TRY(feed_halos({}, nh_p_grad, [&]() -> int {
+      if (it == n_split - 1) {
         HALO(FV3_HALO_INTERFACE_U__V, 0);
-      }
-      c->frame_pass = 2;
-      RUN(FV3_OP_NH_P_GRAD, fv3_nh_p_grad_scaled(c, &st->u, &st->v, &ws->pkc, &ws->zh, &ws->pk3, &f_delp[cur], dt, ptop, akap, c->cst.grav, stream));
-      if (cf.rf_fast) RUN(FV3_OP_RAY_FAST, fv3_ray_fast(c, &st->u, &st->v, &f_w[cur], dt, ptop, stream));
-      c->frame_pass = 0;
-      if (it == n_split - 1) HALO(FV3_HALO_INTERFACE_U__V, 1);
-    } else {
-      // (the reference stores gz = g * zh first -- compute_geopotential; here the corner interpolation reads zh and scales it)
-      RUN(FV3_OP_NH_P_GRAD, fv3_nh_p_grad_scaled(c, &st->u, &st->v, &ws->pkc, &ws->zh, &ws->pk3, &f_delp[cur], dt, ptop, akap, c->cst.grav, stream));
-      if (cf.rf_fast) RUN(FV3_OP_RAY_FAST, fv3_ray_fast(c, &st->u, &st->v, &f_w[cur], dt, ptop, stream));
-      if (it != n_split - 1) {
-        HALO(FV3_HALO_U__V, 0);
       } else {
-        HALO(FV3_HALO_INTERFACE_U__V, 0);
-        HALO(FV3_HALO_INTERFACE_U__V, 1);
+        HALO(FV3_HALO_U__V, 0);
+        if (frame_first) {  // (only there: w is final too, and the next sub-step finds its update in flight)
+          HALO(FV3_HALO_W, 0);
+          w_started = true;
+        }
       }
-    }
+      return FV3_OK;
+    }));
+    if (it == n_split - 1) HALO(FV3_HALO_INTERFACE_U__V, 1);  // (frame-first: waited for behind the interior pass)
   }
   if (pingpong) {
     // Bring the state home exactly as the in-place sequence leaves it.  delp / pt / q_con: their halos were exchanged after the

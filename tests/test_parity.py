@@ -834,3 +834,97 @@ def test_baroclinic_wave_state(backend):
         assert du < 2.0, f"rank {r}: zonal flow drifted by {du} m/s in one step"
         assert np.abs(got[r]["w"][sl]).max() < 1.0
         assert np.abs(got[r]["pt"][sl] / init[r]["pt"][sl] - 1.0).max() < 5e-3
+
+
+_SEQUENCER_STATE_REFERENCE = {}  # backend -> what a fresh context gives (computed once, never changed)
+
+
+def _standalone_operators_and_a_full_call(sf, part, cfg, grids, init, phis, nz):
+    """c_sw and riem_solver3 on their own (the `stencils` wrappers) and one complete acoustic call on context `sf`, each on fresh copies of the
+    inputs: every output as its WHOLE storage (halos, padding and the level nz included)."""
+    from helpers import DIMS3
+    from pace_amd import stencils
+    from pace_amd.dyn_core import AcousticDynamics, DycoreState
+    from pace_amd.halo import Layout
+
+    qf, c = sf.quantity_factory, get_constants()
+    q3 = lambda arrays: qf.from_array([np.array(a) for a in arrays], DIMS3)  # noqa: E731
+    q2 = lambda arrays: qf.from_array([np.array(a) for a in arrays], ("x", "y"))  # noqa: E731
+    out = {}
+    # c_sw: inside the sequencer it may thin out its ua / va stores and leave windows running on the auxiliary stream
+    names = ("delp", "pt", "u", "v", "w", "uc", "vc", "ua", "va", "omga")
+    Q = {n: q3([s[n] for s in init]) for n in names}
+    T = {n: qf.zeros(DIMS3) for n in ("ut", "vt", "divgd")}
+    delpc, ptc = stencils.CGridShallowWaterDynamics(sf)(*[Q[n] for n in names[:9]], T["ut"], T["vt"], T["divgd"], Q["omga"], 56.25)
+    out.update({"c_sw " + n: x for n, x in list(Q.items()) + list(T.items()) + [("delpc", delpc), ("ptc", ptc)]})
+    # riem_solver3: inside the sequencer it may skip the delz store, run one frame-first pass only, or take update_dz_d's scan as a pre-sweep
+    zs = [p * c.RGRAV for p in phis]
+    zh = []
+    for s, z in zip(init, zs):
+        h = np.zeros_like(s["u"])
+        h[:, :, nz] = z[:, :, 0]
+        for k in range(nz - 1, -1, -1):
+            h[:, :, k] = h[:, :, k + 1] - s["delz"][:, :, k]
+        zh.append(h)
+    names = ("cappa", "delz", "q_con", "delp", "pt", "pe", "pk", "peln", "w")
+    Q = {n: q3([s[n] for s in init]) for n in names}
+    Q.update(zh=q3(zh), ppe=qf.zeros(DIMS3), pk3=qf.zeros(DIMS3))
+    stencils.RiemannSolver3(sf)(1, 18.75, Q["cappa"], grids[0].ptop, q2(zs), q2([np.full_like(z, 0.01) for z in zs]), Q["delz"], Q["q_con"], Q["delp"], Q["pt"],
+                                Q["zh"], Q["pe"], Q["ppe"], Q["pk3"], Q["pk"], Q["peln"], Q["w"])
+    out.update({"riem_solver3 " + n: x for n, x in Q.items()})
+    # one complete call from the initial state, the way every other test makes it
+    st = DycoreState.from_arrays(qf, [dict({k: v.copy() for k, v in s.items()}, phis=p) for s, p in zip(init, phis)])
+    AcousticDynamics(Layout(part, 1, 0), grids, sf, config=cfg, phis=st.phis, state=st)(st, 225.0, n_map=1)
+    out.update({"acoustic " + n: getattr(st, n) for n in STATE})
+    if not sf.hostemu:
+        torch.cuda.synchronize()
+    return {n: x.storage.detach().cpu().numpy().copy() for n, x in out.items()}
+
+
+# (update, phase, which request of that kind) at which the halo callback reports an error: the very first request of the call; the start of
+# delp / pt / q_con behind the first sub-step's d_sw (about its middle); the start of zh behind the first sub-step's riem_solver3 (the first
+# start of zh belongs to the heights of the call); the first request of the second sub-step
+@pytest.mark.parametrize("fail_at", [("q_con__cappa", 0, 1), ("delp__pt__q_con", 0, 1), ("zh", 0, 2), ("w", 0, 2)], ids=lambda f: f"{f[0]}.{f[1]}#{f[2]}")
+def test_failed_acoustic_call_leaves_no_sequencer_state(backend, fail_at):
+    """fv3_acoustic_step tells its operators about the call they are part of (fv3_seq_hints: not the last sub-step, first sub-step, frame-first
+    pass, ...).  None of it may outlive the call, also when the call ends early: after an acoustic call that a failing halo request cut short,
+    c_sw and riem_solver3 on their own and a complete acoustic call give, on the SAME context, bitwise what a fresh context gives -- ua, va and
+    delz (the stores the sequencer's hints thin out or skip) over their whole storages like everything else."""
+    from pace_amd import lib as _lib
+    from pace_amd.dyn_core import AcousticDynamics, DycoreState
+    from pace_amd.halo import Layout
+
+    nz = 5
+    part, cfg, grids, init, phis, _ = oracle_cube(12, (1, 1), nz, dict(n_split=2))
+    make_sf = lambda: stencil_factory_for(backend)(grids, cfg, get_constants())  # noqa: E731
+    if backend not in _SEQUENCER_STATE_REFERENCE:
+        _SEQUENCER_STATE_REFERENCE[backend] = _standalone_operators_and_a_full_call(make_sf(), part, cfg, grids, init, phis, nz)
+    want = _SEQUENCER_STATE_REFERENCE[backend]
+
+    sf = make_sf()
+    st = DycoreState.from_arrays(sf.quantity_factory, [dict({k: v.copy() for k, v in s.items()}, phis=p) for s, p in zip(init, phis)])
+    dyn = AcousticDynamics(Layout(part, 1, 0), grids, sf, config=cfg, phis=st.phis, state=st)
+    dyn._build_native_args(st)
+    c_state, c_work, _, errors = dyn._native_args
+    ups = [dyn._updaters[n] for n in _lib.HALO_UPDATES]
+    seen = []
+
+    def halo(_user, update, phase, stream):  # the test's own callback: forwards to the updaters, reports an error at the chosen request
+        seen.append((_lib.HALO_UPDATES[update], phase))
+        if seen[-1] == fail_at[:2] and seen.count(seen[-1]) == fail_at[2]:
+            return 1
+        (ups[update].start if phase == 0 else ups[update].wait)(stream)
+        return 0
+
+    dyn._native_args = (c_state, c_work, _lib.fv3_halo_fn(halo), errors)
+    with pytest.raises(_lib.Fv3Error, match="halo callback reported an error"):
+        dyn(st, 225.0, n_map=1)
+    assert seen[-1] == fail_at[:2]  # (the call ended at that request ...)
+    assert (len(seen) == 1) == (fail_at[0] == "q_con__cappa") and seen.count(("w", 0)) == {"q_con__cappa": 0, "w": 2}.get(fail_at[0], 1)  # (... in that sub-step)
+    for u in ups:
+        u.wait()  # (what the cut-short call started and never waited for)
+
+    got = _standalone_operators_and_a_full_call(sf, part, cfg, grids, init, phis, nz)
+    assert set(got) == set(want)
+    for n in want:
+        assert np.array_equal(got[n], want[n], equal_nan=True), n
