@@ -484,6 +484,92 @@ typedef struct {
 int fv3_neg_adj3(fv3_ctx *, const fv3_water *water, const fv3_latent *latent, const fv3_field *pt, const fv3_field *delp,
                  void *stream);
 
+/* ---- saturation adjustment (fv3_satadj.hip, fv3_satadj.h; the fused form in fv3_remap.hip) ----------------------------------------
+ * fv_sat_adj (FV3 fv_cmp.F90, the non-hydrostatic form), which FV3 runs inside every remap when do_sat_adj is set: after the remap and
+ * the fill, before moist_cv and pkz.  Phase changes between the six species, the latent heat booked on the temperature.  Restated
+ * from the Fortran; not built: the energy-fixer branch (consv_te = 0), the out_dt tendency, the cloud fraction (do_qa / qa).
+ * In the build's Real, every sum, product and quotient rounded on its own in the order written, left to right; exp and log are the
+ * build's; min(a, b) = a < b ? a : b, max(a, b) = a > b ? a : b, of three: min(min(a, b), c), max(max(a, b), c); dim(a, b) = max(a - b, 0).
+ * Constants, formed in double and cast once: cv_air .. li00 as in fv3_neg_adj3; zvir = rvgas / rdgas - 1, rvgas, grav (the context's);
+ * tice = t_ice; tice0 = t_ice - 0.01; t_wfr = t_ice - 40; lat2 = (hlv + hlf)^2; mdt: the remap interval (s); sdt = 0.5 mdt; dt_bigg = mdt;
+ *   fac_X = 1 - exp(-mdt / tau_X) for X = i2s, r2g, l2r, smlt;  fac_X = 1 - exp(-sdt / tau_X) for X = v2l, imlt;
+ *   fac_l2v = min(sat_adj0, 1 - exp(-sdt / tau_l2v)).
+ * Shorthands: cvm = ((mc_air + qv * cv_vap) + q_liq * c_liq) + q_sol * c_ice;  heat(s, L): cvm again, then pt1 = pt1 + s * L / cvm;
+ *   lat: lhl = lv00 + d0_vap * pt1; lhi = li00 + dc_ice * pt1; lcp2 = lhl / cvm; icp2 = lhi / cvm.
+ * Per cell (tv = T (1 + zvir qv)(1 - q_con) in and out; dp = delp; delz):
+ *    1  q_liq = ql + qr; q_sol = (qi + qs) + qg; qpz = q_liq + q_sol; pt1 = tv / ((1 + zvir * qv) * (1 - qpz)); qpz = qpz + qv;
+ *       den = dp / (-grav * delz); mc_air = (1 - qpz) * cv_air; cvm; lat
+ *    2  qi < 0: qs += qi; qi = 0
+ *    3  qi > 1e-8 and pt1 > tice: sink = min(qi, fac_imlt * (pt1 - tice) / icp2); qi -= sink; tmp = min(sink, dim(ql_mlt, ql));
+ *       ql += tmp; qr += sink - tmp; q_liq += sink; q_sol -= sink; heat(-sink, lhi); lat
+ *    4  qs < 0: qg += qs; qs = 0;  else qg < 0: tmp = min(-qg, max(0, qs)); qg += tmp; qs -= tmp
+ *    5  ql < 0: tmp = min(-ql, max(0, qr)); ql += tmp; qr -= tmp;  else qr < 0: tmp = min(-qr, max(0, ql)); ql -= tmp; qr += tmp
+ *    6  dtmp = (tice - 48) - pt1; ql > 0 and dtmp > 0: sink = min(ql, ql * dtmp * 0.125, dtmp / icp2); ql -= sink; qi += sink;
+ *       q_liq -= sink; q_sol += sink; heat(sink, lhi); lat
+ *    7  (wqsat, dq2dt) = wqs2(pt1, den); dq0 = (qv - wqsat) / (1 + lcp2 * dq2dt);
+ *       dq0 > 0: src = min(sat_adj0 * dq0, max(ql_gen - ql, fac_v2l * dq0));
+ *       else factor = -min(1, fac_l2v * 10 * (1 - qv / wqsat)); src = -min(ql, factor * dq0);
+ *       qv -= src; ql += src; q_liq += src; heat(src, lhl); lat
+ *    8  last_step only: step 7 again with src = dq0 where dq0 > 0
+ *    9  dtmp = t_wfr - pt1; as step 6
+ *   10  tc = tice0 - pt1; ql > 0 and tc > 0: sink = 3.3333e-10 * dt_bigg * (exp(0.66 * tc) - 1) * den * ql * ql;
+ *       sink = min(ql, tc / icp2, sink); the updates of step 6; heat(sink, lhi); lat
+ *   11  dtmp = (tice - 0.1) - pt1; qr > 1e-7 and dtmp > 0: x = dtmp * 0.025; tmp = min(1, x * x) * qr; sink = min(tmp, fac_r2g * dtmp / icp2);
+ *       qr -= sink; qg += sink; q_liq -= sink; q_sol += sink; heat(sink, lhi); lat
+ *   12  dtmp = pt1 - (tice + 0.1); qs > 1e-7 and dtmp > 0: x = dtmp * 0.1; tmp = min(1, x * x) * qs; sink = min(tmp, fac_smlt * dtmp / icp2);
+ *       tmp = min(sink, dim(qs_mlt, ql)); qs -= sink; ql += tmp; qr += sink - tmp; q_liq += sink; q_sol -= sink; heat(-sink, lhi)
+ *   13  ql > ql0_max: sink = fac_l2r * (ql - ql0_max); qr += sink; ql -= sink.  Then lat; tcp2 = lcp2 + icp2
+ *   14  src = 0;  pt1 < t_sub: src = dim(qv, 1e-6);
+ *       else pt1 < tice0: (qsi, dqsdt) = iqs2(pt1, den); dq = qv - qsi; sink = sat_adj0 * dq / (1 + tcp2 * dqsdt);
+ *         pidep = qi > 1e-8 ? sdt * dq * 349138.78 * exp(0.875 * log(qi * den)) / (qsi * den * lat2 / (0.0243 * rvgas * pt1 * pt1) + 4.42478e4) : 0;
+ *         dq > 0: tmp = tice - pt1; qi_crt = qi_gen * min(qi_lim, 0.1 * tmp) / den; src = min(sink, max(qi_crt - qi, pidep), tmp / tcp2);
+ *         else pidep = pidep * min(1, dim(pt1, t_sub) * 0.2); src = max(pidep, sink, -qi);
+ *       qv -= src; qi += src; q_sol += src; heat(src, lhl + lhi)
+ *   15  tv = pt1 * (1 + zvir * qv) * (1 - (q_liq + q_sol))
+ *   16  qg < 0: tmp = min(-qg, max(0, qi)); qg += tmp; qi -= tmp
+ *   17  qim = qi0_max / den; qi > qim: sink = fac_i2s * (qi - qim); qi -= sink; qs += sink
+ * The q_con and cappa that are stored are moist_cv of the final species (the formulas above), not the sums step 15 forms in passing.
+ * Saturation tables (FV3 qs_init; four arrays of 2621 entries, entry n = 1 .. 2621 at T_n = (t_ice - 160) + 0.1 (n - 1), formed in
+ * double on the host and cast): tablew[n] = e00 * exp((dc_vap * log(T_n / t_ice) + lv0 * (T_n - t_ice) / (T_n * t_ice)) / rvgas) with
+ * e00 = 611.21, dc_vap = (cv_vap + rvgas) - c_liq, lv0 = hlv - dc_vap * t_ice; table2[n]: for n <= 1600 the same with dc_vap + dc_ice
+ * and lv0 + li00, above that tablew[n], entries 1600 and 1601 replaced by 0.25 * (t[n-1] + 2 t[n] + t[n+1]) of the unsmoothed values;
+ * desw[n] = max(0, tablew[n+1] - tablew[n]) of the cast entries, the last entry repeating the one before it; des2 likewise.
+ * Lookup: ap1 = min(2621, 10 * dim(T, tice - 160) + 1); it = floor(ap1); es = tab[it] + (ap1 - it) * des[it]; qs = es / (rvgas * T * den);
+ * it = max(1, floor(ap1 - 0.5)); dqdt = 10 * (des[it] + (ap1 - it) * (des[it+1] - des[it])) / (rvgas * T * den).  wqs2: tablew, desw; iqs2: table2, des2.
+ * The tables are built by the context's first adjusting call, in device memory the context owns; a later call allocates nothing. */
+typedef struct {
+  double tau_i2s, tau_v2l, tau_l2v, tau_imlt, tau_r2g, tau_smlt, tau_l2r; /* time scales (s): 1000, 150, 300, 600, 900, 900, 900 */
+  double ql_gen, qi_gen, qi_lim, ql_mlt, qs_mlt, ql0_max, qi0_max;       /* 1e-3, 1.82e-6, 1, 2e-3, 1e-6, 2e-3, 1e-4 */
+  double sat_adj0, t_sub;                                                /* 0.9, 184 */
+} fv3_sat_params;
+
+/* fv3_sat_adj: the adjustment alone, in place on the compute cells 1..nx x 1..ny of levels kmp .. nz-1, where kmp is the first level
+ * whose reference mid-pressure pfull_k = (ph_{k+1} - ph_k) / log(ph_{k+1} / ph_k), ph = ak + bk * 1e5, exceeds 10 hPa (formed in double
+ * from the context's ak / bk; fv3_sat_adj_level0 returns it).  tv (in, out), the six species (in, out); q_con, cappa, pkz (out):
+ * moist_cv of the adjusted species and pkz = exp(cappa * log(rrg * delp / delz * tv)); delp and delz are only read.  Nothing is read or
+ * written above kmp, in the halo or on the pad level.
+ * FV3_ERR_ARG (a message that names the field, nothing launched, no field changed): a null context, fv3_water, fv3_latent or
+ * fv3_sat_params; any species NULL; a null or wrongly shaped field; a field given twice (among tv, delp, delz, q_con, cappa, pkz and the
+ * species); mdt <= 0; last_step other than 0 / 1; a tau_* that is not positive.
+ * fv3_sat_adj_tables: tablew, table2, desw, des2 one after the other as the kernels hold them, widened to double; n must be 4 * 2621;
+ * FV3_ERR_ARG before the context's first adjusting call (the tables are made of that call's constants). */
+int fv3_sat_adj(fv3_ctx *, const fv3_water *water, const fv3_latent *latent, const fv3_sat_params *params, const fv3_field *tv,
+                const fv3_field *delp, const fv3_field *delz, const fv3_field *q_con, const fv3_field *cappa, const fv3_field *pkz,
+                double mdt, int last_step, void *stream);
+int fv3_sat_adj_level0(fv3_ctx *, int *kmp);
+int fv3_sat_adj_tables(fv3_ctx *, double *out, long n);
+
+/* fv3_remap_moist_sat: fv3_remap_moist with the adjustment where FV3 has it, inside the closing column kernel: on the levels
+ * kmp .. nz-1 the remapped and filled species and the remapped T_v go through the cell step above before moist_cv and pkz are formed;
+ * no extra pass over the fields.  Bit for bit fv3_remap_moist, then fv3_sat_adj on tv = pt * pkz, then pt = tv / pkz (to that end the
+ * kernel forms the unadjusted pkz of such a cell first and starts from tv = (T_v / pkz) * pkz).  All six species are needed.
+ * FV3_ERR_ARG: what fv3_remap_moist and fv3_sat_adj reject. */
+int fv3_remap_moist_sat(fv3_ctx *, int n_tracers, const fv3_field *const *tracers, const fv3_field *pt, const fv3_field *delp,
+                        const fv3_field *delz, const fv3_field *peln, const fv3_field *pe, const fv3_field *pk, const fv3_field *pkz,
+                        const fv3_field *u, const fv3_field *v, const fv3_field *w, const fv3_field *cappa, const fv3_field *q_con,
+                        const fv3_field *ps, const fv3_field *wsd, const fv3_water *water, int fill, const fv3_latent *latent,
+                        const fv3_sat_params *params, double mdt, int last_step, void *stream);
+
 /* CubedToLatLon (the last operator of fv_dynamics: FV3 fv_grid_utils.F90 c2l_ord4 / c2l_ord2; pyFV3 CubedToLatLon, savepoint
  * FVDynamics-Out ua / va [REF tests/savepoint/thresholds/fv_dynamics.yaml]).  D-grid u, v -> ua, va on the compute cells in earth
  * coordinates (eastward, northward).  order: c2l_ord, 4 (the reference's default) or 2.  a11 .. a22: the cell-centre rotation

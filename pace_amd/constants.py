@@ -97,6 +97,12 @@ C_ICE = 1972.0
 HLV = 2.5e6
 HLF = 3.3358e5
 T_ICE = 273.16
+# Namelist defaults of the saturation adjustment (FV3 fv_cmp.F90 / gfdl_cloud_microphys.F90; ``fv3_sat_params`` in include/fv3_mi355x.h):
+# the time scales tau_* in seconds, the thresholds in kg/kg, t_sub in K.  Restated from memory ("Uncertain restatements").
+SAT_ADJ_DEFAULTS = dict(
+    tau_i2s=1000.0, tau_v2l=150.0, tau_l2v=300.0, tau_imlt=600.0, tau_r2g=900.0, tau_smlt=900.0, tau_l2r=900.0,
+    ql_gen=1.0e-3, qi_gen=1.82e-6, qi_lim=1.0, ql_mlt=2.0e-3, qs_mlt=1.0e-6, ql0_max=2.0e-3, qi0_max=1.0e-4, sat_adj0=0.9, t_sub=184.0,
+)
 
 _SETS = {"GFS": GFS, "GFDL": GFDL, "GEOS": GEOS}
 

@@ -279,6 +279,11 @@ struct fv3_ctx {
   void *xfer_user = nullptr;
   fv3_halo_plan *halo_plans[FV3_HALO_COUNT] = {nullptr};
   Real *ak_dev = nullptr, *bk_dev = nullptr;  // hybrid-coordinate tables on the device (fv3_remap.hip)
+  // saturation tables of fv3_sat_adj / fv3_remap_moist_sat (fv3_satadj.hip): built on first use, the host copy is what the device holds;
+  // sat_key: the constants they were built from
+  Real *sat_tab = nullptr;
+  std::vector<Real> sat_tab_h;
+  double sat_key[7] = {0, 0, 0, 0, 0, 0, 0};
   // Sink for the stores of lanes / rows a marching wave does not own (-DFV3_USTORE experiment builds only; see fv3_store_sel)
   Real *trash = nullptr;
   // Ping-pong of the four scalars d_sw rewrites (delp, pt, w, q_con; fv3_step.hip): d_sw's marches read the old fields through

@@ -22,15 +22,20 @@ struct MoistCell {
 // an optional species at element p of its field (the test is uniform over the launch)
 FV3_HD inline Real moist_opt(const Real *f, long p) { return f ? f[p] : (Real)0; }
 
-FV3_HD inline MoistCell moist_cell(const MoistIn &m, long p) {
+// the three values from the six species of a cell held in registers (the one place the formulas stand)
+FV3_HD inline MoistCell moist_values(const MoistIn &m, Real qv, Real qliquid, Real qrain, Real qice, Real qsnow, Real qgraupel) {
   MoistCell o;
-  o.qv = m.qv[p];
-  const Real ql = moist_opt(m.ql, p) + moist_opt(m.qr, p);
-  const Real qs = (moist_opt(m.qi, p) + moist_opt(m.qs, p)) + moist_opt(m.qg, p);
+  o.qv = qv;
+  const Real ql = qliquid + qrain;
+  const Real qs = (qice + qsnow) + qgraupel;
   o.q_con = ql + qs;
   o.cvm = ((((Real)1.0 - (o.qv + o.q_con)) * m.cv_air + o.qv * m.cv_vap) + ql * m.c_liq) + qs * m.c_ice;
   o.cappa = m.rdgas / (m.rdgas + o.cvm / ((Real)1.0 + m.zvir * o.qv));
   return o;
+}
+
+FV3_HD inline MoistCell moist_cell(const MoistIn &m, long p) {
+  return moist_values(m, m.qv[p], moist_opt(m.ql, p), moist_opt(m.qr, p), moist_opt(m.qi, p), moist_opt(m.qs, p), moist_opt(m.qg, p));
 }
 
 struct MoistNamed {

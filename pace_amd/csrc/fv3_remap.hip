@@ -11,6 +11,10 @@
 // thickness), q_con and cappa from the remapped and filled species, then pkz with the new cappa.  One body (remap_all) serves both
 // entries; the closing column kernel is templated on "moist".
 //
+// fv3_remap_moist_sat is the moist remap with FV3's saturation adjustment (fv_sat_adj, fv3_satadj.h) where FV3 has it: after the remap
+// and the fill, before moist_cv and pkz, inside the same closing column kernel (templated on "satadj" as well), on the levels below
+// 10 hPa.  fv3_remap and fv3_remap_moist run no saturation adjustment.
+//
 // A thread owns a column (i fastest: every level access of a wave is one coalesced row).  What a column needs beyond
 // O(1) registers are the edge values of the parabolas (a tridiagonal solve in k): two scratch fields (the elimination factors
 // and the edge values); the limited parabola of a source layer is a function of the edge values and five neighbouring means
@@ -19,6 +23,7 @@
 // with last_call, edge_pe for the ring the D-grid winds average over); the Eulerian ones are ak + bk * ps on the fly.
 #include "fv3_moist.h"
 #include "fv3_ops.h"
+#include "fv3_satadj.h"
 
 namespace {
 
@@ -315,8 +320,11 @@ struct CloseArgs {
 // The closing column kernel: Eulerian pressures, pkz from the remapped T_v, pt back to the loop's form, the new layer thickness.
 // MOIST: q_con and cappa of every level are formed from the remapped (and filled) species first (moist_cv, fv3_moist.h), stored, and
 // the new cappa is the one pkz is built with; otherwise cappa is the given field.
-template <bool MOIST>
-void remap_close(fv3_ctx *c, fv3_stream_t s, const CloseArgs a, const MoistIn m) {
+// SATADJ (with MOIST): on the levels kmp .. nz-1 the six species and T_v of the cell go through the saturation adjustment (sat_adj_cell,
+// fv3_satadj.h) on their way into moist_cv: six more fields read and written, no other read added.  The cell starts from
+// tv = (T_v / pkz) * pkz with the unadjusted pkz, which is what fv3_remap_moist followed by fv3_sat_adj on pt * pkz starts from.
+template <bool MOIST, bool SATADJ = false>
+void remap_close(fv3_ctx *c, fv3_stream_t s, const CloseArgs a, const MoistIn m, const SatK sk = SatK{}, const SatFields sf = SatFields{}) {
   const Geo g = c->g;
   const int km = g.nz;
   Real *const pt = a.pt, *const delp = a.delp, *const delz = a.delz, *const peln = a.peln, *const pe = a.pe, *const pk = a.pk, *const pkz = a.pkz, *const cappa = a.cappa;
@@ -334,17 +342,41 @@ void remap_close(fv3_ctx *c, fv3_stream_t s, const CloseArgs a, const MoistIn m)
     for (int k = 0; k < km; ++k) {
       const Real p1 = k + 1 == km ? psv : ak[k + 1] + bk[k + 1] * psv;
       const Real dp2 = p1 - p0;
-      Real cp;
-      if constexpr (MOIST) {
-        const MoistCell o = moist_cell(m, tb + (long)k * g.sk + pix);
+      Real cp, tv, dz = (Real)0;  // (dz: the adjusting form reads delz once, ahead of the cell step)
+      if constexpr (MOIST && SATADJ) {
+        MoistCell o;
+        tv = RK(TV, k);
+        dz = RK(delz, k);
+        if (k >= sk.kmp) {
+          Real qv = RK(sf.qv, k), ql = RK(sf.ql, k), qr = RK(sf.qr, k), qi = RK(sf.qi, k), qs = RK(sf.qs, k), qg = RK(sf.qg, k);
+          const Real pz0 = exp(moist_values(m, qv, ql, qr, qi, qs, qg).cappa * log(rrg * dp2 / dz * tv));
+          tv = tv / pz0 * pz0;
+          sat_adj_cell(sk, tv, qv, ql, qr, qi, qs, qg, dp2, dz);
+          o = moist_values(m, qv, ql, qr, qi, qs, qg);
+          RK(sf.qv, k) = qv;
+          RK(sf.ql, k) = ql;
+          RK(sf.qr, k) = qr;
+          RK(sf.qi, k) = qi;
+          RK(sf.qs, k) = qs;
+          RK(sf.qg, k) = qg;
+        } else {
+          o = moist_cell(m, tb + (long)k * g.sk + pix);
+        }
         RK(q_con, k) = o.q_con;
         RK(cappa, k) = o.cappa;
         cp = o.cappa;
       } else {
-        cp = RK(cappa, k);
+        if constexpr (MOIST) {
+          const MoistCell o = moist_cell(m, tb + (long)k * g.sk + pix);
+          RK(q_con, k) = o.q_con;
+          RK(cappa, k) = o.cappa;
+          cp = o.cappa;
+        } else {
+          cp = RK(cappa, k);
+        }
+        tv = RK(TV, k);
       }
-      const Real tv = RK(TV, k);
-      const Real pz = exp(cp * log(rrg * dp2 / RK(delz, k) * tv));
+      const Real pz = exp(cp * log(rrg * dp2 / (MOIST && SATADJ ? dz : RK(delz, k)) * tv));
       RK(pkz, k) = pz;
       RK(pt, k) = tv / pz;
       RK(delp, k) = dp2;
@@ -365,16 +397,17 @@ void remap_close(fv3_ctx *c, fv3_stream_t s, const CloseArgs a, const MoistIn m)
 // fv3_remap (water == nullptr: q_con_ and fill are not read) and fv3_remap_moist
 int remap_all(fv3_ctx *c, int n_tracers, const fv3_field *const *tracers, const fv3_field *pt_, const fv3_field *delp_, const fv3_field *delz_, const fv3_field *peln_,
               const fv3_field *pe_, const fv3_field *pk_, const fv3_field *pkz_, const fv3_field *u_, const fv3_field *v_, const fv3_field *w_, const fv3_field *cappa_,
-              const fv3_field *q_con_, const fv3_field *ps_, const fv3_field *wsd_, const fv3_water *water, int fill, void *stream) {
+              const fv3_field *q_con_, const fv3_field *ps_, const fv3_field *wsd_, const fv3_water *water, int fill, void *stream, const SatK *sat = nullptr, const SatFields *satf = nullptr) {
+  const std::string op = sat ? "remap_moist_sat" : "remap_moist";
   if (water) {  // (fv3_remap_moist has checked the context)
-    if (n_tracers < 0) return fv3_fail(c, FV3_ERR_ARG, "remap_moist: n_tracers = " + std::to_string(n_tracers) + " is negative");
-    if (n_tracers > 0 && !tracers) return fv3_fail(c, FV3_ERR_ARG, "remap_moist: the tracer list is null with n_tracers = " + std::to_string(n_tracers));
+    if (n_tracers < 0) return fv3_fail(c, FV3_ERR_ARG, op + ": n_tracers = " + std::to_string(n_tracers) + " is negative");
+    if (n_tracers > 0 && !tracers) return fv3_fail(c, FV3_ERR_ARG, op + ": the tracer list is null with n_tracers = " + std::to_string(n_tracers));
   }
   if (!c || n_tracers < 0 || (n_tracers && !tracers)) return FV3_ERR_ARG;
   FV3_FIELD(pt, pt_) FV3_FIELD(delp, delp_) FV3_FIELD(delz, delz_) FV3_FIELD(peln, peln_) FV3_FIELD(pe, pe_) FV3_FIELD(pk, pk_) FV3_FIELD(pkz, pkz_)
   FV3_FIELD(u, u_) FV3_FIELD(v, v_) FV3_FIELD(w, w_) FV3_FIELD(cappa, cappa_) FV3_FIELD2D(ps, ps_) FV3_FIELD2D(wsd, wsd_)
   const Geo g = c->g;
-  if (g.nz < 5) return fv3_fail(c, FV3_ERR_UNSUPPORTED, std::string(water ? "remap_moist" : "remap") + ": needs at least 5 levels (two monotone layers at either end + an interior)");
+  if (g.nz < 5) return fv3_fail(c, FV3_ERR_UNSUPPORTED, (water ? op : std::string("remap")) + ": needs at least 5 levels (two monotone layers at either end + an interior)");
   std::vector<Real *> q(n_tracers);
   for (int n = 0; n < n_tracers; ++n) {
     q[n] = fv3_chk(c, tracers[n], "tracer");
@@ -383,7 +416,7 @@ int remap_all(fv3_ctx *c, int n_tracers, const fv3_field *const *tracers, const 
   MoistIn m{};
   Real *q_con = nullptr;
   if (water) {
-    if (int st = fv3_moist_in(c, "remap_moist", water, &m)) return st;
+    if (int st = fv3_moist_in(c, op.c_str(), water, &m)) return st;
     q_con = fv3_chk(c, q_con_, "q_con_");
     if (!q_con) return FV3_ERR_ARG;
     // the species are what gets remapped and filled: each one is one of the tracers; a tracer given twice would be remapped twice
@@ -392,18 +425,18 @@ int remap_all(fv3_ctx *c, int n_tracers, const fv3_field *const *tracers, const 
     for (int a = 0; a < n_sp; ++a) {
       bool found = false;
       for (int n = 0; n < n_tracers; ++n) found = found || q[n] == sp[a].ptr;
-      if (!found) return fv3_fail(c, FV3_ERR_ARG, std::string("remap_moist: ") + sp[a].name + " is not among the tracers (the species are the fields that get remapped)");
+      if (!found) return fv3_fail(c, FV3_ERR_ARG, op + ": " + sp[a].name + " is not among the tracers (the species are the fields that get remapped)");
     }
     for (int n = 0; n < n_tracers; ++n)
       for (int l = 0; l < n; ++l)
-        if (q[l] == q[n]) return fv3_fail(c, FV3_ERR_ARG, "remap_moist: tracers " + std::to_string(l) + " and " + std::to_string(n) + " are the same field");
+        if (q[l] == q[n]) return fv3_fail(c, FV3_ERR_ARG, op + ": tracers " + std::to_string(l) + " and " + std::to_string(n) + " are the same field");
     // q_con is written beside fields that are read and written by the same kernels: it may be none of them
     const MoistNamed other[] = {{"pt", pt}, {"delp", delp}, {"delz", delz}, {"peln", peln}, {"pe", pe}, {"pk", pk}, {"pkz", pkz}, {"u", u}, {"v", v}, {"w", w}, {"cappa", cappa}};
     for (const MoistNamed &o : other)
-      if (o.ptr == q_con) return fv3_fail(c, FV3_ERR_ARG, std::string("remap_moist: q_con is the ") + o.name + " field");
+      if (o.ptr == q_con) return fv3_fail(c, FV3_ERR_ARG, op + ": q_con is the " + o.name + " field");
     for (int n = 0; n < n_tracers; ++n) {
-      if (q[n] == q_con) return fv3_fail(c, FV3_ERR_ARG, "remap_moist: q_con is tracer " + std::to_string(n));
-      if (q[n] == cappa) return fv3_fail(c, FV3_ERR_ARG, "remap_moist: cappa is tracer " + std::to_string(n));
+      if (q[n] == q_con) return fv3_fail(c, FV3_ERR_ARG, op + ": q_con is tracer " + std::to_string(n));
+      if (q[n] == cappa) return fv3_fail(c, FV3_ERR_ARG, op + ": cappa is tracer " + std::to_string(n));
     }
   }
   fv3_stream_t s = (fv3_stream_t)stream;
@@ -493,11 +526,13 @@ int remap_all(fv3_ctx *c, int n_tracers, const fv3_field *const *tracers, const 
   }
   // ---- Eulerian pressures, pkz from the remapped T_v, pt back to the loop's form, the new layer thickness
   const CloseArgs ca{pt, delp, delz, peln, pe, pk, pkz, cappa, ps, TV, ak, bk, q_con, ptop, akap, rrg};
-  if (water)
+  if (sat)
+    remap_close<true, true>(c, s, ca, m, *sat, *satf);
+  else if (water)
     remap_close<true>(c, s, ca, m);
   else
     remap_close<false>(c, s, ca, m);
-  return fv3_post(c, s, water ? "remap_moist" : "remap");
+  return fv3_post(c, s, water ? op.c_str() : "remap");
 }
 
 }  // namespace
@@ -514,4 +549,15 @@ extern "C" int fv3_remap_moist(fv3_ctx *c, int n_tracers, const fv3_field *const
   if (!c) return fv3_fail(c, FV3_ERR_ARG, "remap_moist: the context is null");
   if (!water) return fv3_fail(c, FV3_ERR_ARG, "remap_moist: the fv3_water is null");
   return remap_all(c, n_tracers, tracers, pt, delp, delz, peln, pe, pk, pkz, u, v, w, cappa, q_con, ps, wsd, water, fill, stream);
+}
+
+extern "C" int fv3_remap_moist_sat(fv3_ctx *c, int n_tracers, const fv3_field *const *tracers, const fv3_field *pt, const fv3_field *delp, const fv3_field *delz,
+                                   const fv3_field *peln, const fv3_field *pe, const fv3_field *pk, const fv3_field *pkz, const fv3_field *u, const fv3_field *v, const fv3_field *w,
+                                   const fv3_field *cappa, const fv3_field *q_con, const fv3_field *ps, const fv3_field *wsd, const fv3_water *water, int fill, const fv3_latent *latent,
+                                   const fv3_sat_params *params, double mdt, int last_step, void *stream) {
+  if (!c) return fv3_fail(c, FV3_ERR_ARG, "remap_moist_sat: the context is null");
+  SatK k;
+  SatFields f;
+  if (int st = fv3_sat_setup(c, "remap_moist_sat", water, latent, params, mdt, last_step, &k, &f)) return st;
+  return remap_all(c, n_tracers, tracers, pt, delp, delz, peln, pe, pk, pkz, u, v, w, cappa, q_con, ps, wsd, water, fill, stream, &k, &f);
 }

@@ -11,7 +11,9 @@ the vertical filling of negative tracer values at the end of the remap with ``dy
 (needs ``--temperature --remap`` and ``nwat: 6``) the first six tracers are the water species, ``q_con`` and ``cappa`` follow them through
 ``moist_cv`` and the start-up line and the json say ``"thermodynamics": "moist_cv"`` (otherwise ``"given"``); with ``--neg-adj`` (needs
 ``--moist``) FV3's ``neg_adj3`` fixes negative water species after the conversion back to temperature and the start-up line and the json
-say ``"neg_adj": true`` (otherwise ``false``) -- and writes
+say ``"neg_adj": true`` (otherwise ``false``); with ``--moist`` and ``do_sat_adj: true`` in the yaml (or ``--sat-adj on``; ``--sat-adj off``
+overrides the yaml) FV3's saturation adjustment runs inside every remap with the yaml's ``tau_*`` / ``ql_gen`` ... keys
+(``pace_amd.stencils.SatAdjustConfig``) and the start-up line and the json say ``"sat_adj": true`` (otherwise ``false``) -- and writes
 the per-step times in the layout the reference's performance collector uses
 (``{"times": {<timer>: {"hits": n, "times": [[...per step...] per rank]}}}``, timers ``mainloop``, ``DynCore``,
 ``TracerAdvection``, ``Remapping`` [REF tests/main/driver/test_driver.py:77-121]).  With ``--tracers N --remap`` the step is the
@@ -46,6 +48,24 @@ import sys
 import yaml
 
 
+def _sat_adj_keys():
+    from .constants import SAT_ADJ_DEFAULTS
+
+    return ("do_sat_adj",) + tuple(SAT_ADJ_DEFAULTS)
+
+
+SAT_ADJ_KEYS = _sat_adj_keys()
+
+
+def resolve_sat_adj(option: str, sat_block: dict, moist: bool) -> bool:
+    """Whether every remap of the step runs the saturation adjustment: the yaml's ``dycore_config.do_sat_adj`` (absent = false) unless
+    ``--sat-adj on|off`` overrides it; it works on the six water species of ``--moist`` and is off without it."""
+    if option not in ("yaml", "on", "off"):
+        raise ValueError(f"--sat-adj {option!r}: yaml, on or off")
+    want = bool(sat_block.get("do_sat_adj", False)) if option == "yaml" else option == "on"
+    return bool(want and moist)
+
+
 def load_config(path: str):
     with open(path) as f:
         y = yaml.safe_load(f)
@@ -60,6 +80,8 @@ def load_config(path: str):
     dt_atmos = float(y["dt_atmos"])
     run = dict(
         nwat=(y.get("dycore_config") or {}).get("nwat", None),
+        # the saturation adjustment: do_sat_adj and the keys of SatAdjustConfig as the yaml has them (read with --moist only)
+        sat_adj={k: v for k, v in (y.get("dycore_config") or {}).items() if k in SAT_ADJ_KEYS},
         nx_tile=int(y["nx_tile"]),
         nz=int(y["nz"]),
         layout=tuple(int(v) for v in y.get("layout", (1, 1))),
@@ -143,6 +165,9 @@ def main(argv=None):
     ap.add_argument("--neg-adj", action="store_true",
                     help="neg_adj3 at the end of the thermodynamic part of every step (needs --moist): negative condensate is paid for out of another phase with the latent heat "
                          "booked on the temperature, negative vapour is repaid from the layer below")
+    ap.add_argument("--sat-adj", choices=("yaml", "on", "off"), default="yaml",
+                    help="saturation adjustment (FV3 fv_sat_adj) inside every remap (needs --moist): yaml = dycore_config.do_sat_adj (absent: off) with the yaml's tau_* / ql_gen ... keys; "
+                         "on / off override it")
     ap.add_argument("--diagnostics-path", default=None, help="directory of the diagnostics (overrides diagnostics_config.path of the yaml)")
     ap.add_argument("--no-diagnostics", action="store_true", help="ignore the yaml's diagnostics_config block")
     a = ap.parse_args(argv)
@@ -152,12 +177,20 @@ def main(argv=None):
         sys.exit("--moist needs --temperature --remap: moist_cv sits in the preamble and the remap of DynamicalCore.step_dynamics")
     if a.neg_adj and not a.moist:
         sys.exit("--neg-adj needs --moist: neg_adj3 works on the six water species of the moist step")
+    if a.sat_adj == "on" and not a.moist:
+        sys.exit("--sat-adj on needs --moist: the saturation adjustment works on the six water species of the moist step")
     run, dy, ignored = load_config(a.config)
     if a.moist:
         if run["nwat"] is None or int(run["nwat"]) != 6:
             sys.exit(f"--moist needs dycore_config.nwat: 6 in the yaml (it has nwat: {run['nwat']}): moist_cv is built for the six-species formula only")
         a.tracers = max(a.tracers, 6)
-        ignored = [k for k in ignored if k != "nwat"]  # (read above; without --moist it stays in the list of keys not read)
+        ignored = [k for k in ignored if k != "nwat" and k not in SAT_ADJ_KEYS]  # (read here; without --moist they stay in the list of keys not read)
+    sat_adj = resolve_sat_adj(a.sat_adj, run["sat_adj"], a.moist)
+    sat_cfg = None
+    if sat_adj:
+        from .stencils import SatAdjustConfig
+
+        sat_cfg = SatAdjustConfig(**{k: float(v) for k, v in run["sat_adj"].items() if k != "do_sat_adj"})
 
     import torch
 
@@ -183,6 +216,9 @@ def main(argv=None):
                                          else "  (q_con and cappa are the state's fields as initialised; --moist --temperature --remap: moist_cv of six water species)"))
     say(f'"neg_adj": {str(bool(a.neg_adj)).lower()}' + ("  (neg_adj3 on the temperature and the six water species after the last remap of every step)" if a.neg_adj
                                                          else "  (negative water species stay as the remap leaves them; --moist --neg-adj: neg_adj3)"))
+    say(f'"sat_adj": {str(sat_adj).lower()}' + ("" if a.sat_adj == "yaml" else f" (--sat-adj {a.sat_adj})")
+        + ("  (fv_sat_adj on the six water species inside every remap, between the fill and moist_cv)" if sat_adj
+           else "  (no phase changes; --moist with do_sat_adj: true in the yaml or --sat-adj on: fv_sat_adj inside every remap)"))
     if run["init"] == "analytic" and str(run["case"]).startswith("baroclinic"):
         init = "baroclinic"
         say("initialization: JW2006 baroclinic wave (pace_amd.init.baroclinic_state; restated from the paper, see its docstring)")
@@ -204,7 +240,7 @@ def main(argv=None):
     kw = {k: dy[k] for k in ("k_split", "n_split") if k in dy}
     h = DycoreHarness(nx_tile=run["nx_tile"], nz=run["nz"], layout=run["layout"], dt_atmos=run["dt_atmos"], world_size=world, proc=rank,
                       device=f"cuda:{local_rank}", dtype=dtype, verbose=(rank == 0), init=init, config_overrides={k: v for k, v in dy.items() if k not in ("k_split", "n_split", "fill")},
-                      n_tracers=a.tracers, hord_tr=int(dy.get("hord_tr", 8)), remap=a.remap, fill=fill, latlon_winds=a.latlon_winds, temperature=a.temperature, moist=a.moist, neg_adj=a.neg_adj, **kw)
+                      n_tracers=a.tracers, hord_tr=int(dy.get("hord_tr", 8)), remap=a.remap, fill=fill, latlon_winds=a.latlon_winds, temperature=a.temperature, moist=a.moist, neg_adj=a.neg_adj, sat_adj=sat_adj, sat_adjust_config=sat_cfg, **kw)
     if run["device_sync"]:
         h.sf.set_device_sync(True)
     if a.restart:
@@ -291,18 +327,18 @@ def main(argv=None):
         sdpd = run["dt_atmos"] / mean
         out = a.out or f"{run['experiment']}_fv3_mi355x.json"
         json.dump({"setup": {"experiment": run["experiment"], "nx_tile": run["nx_tile"], "nz": run["nz"], "layout": list(run["layout"]), "dt_atmos": run["dt_atmos"],
-                             "k_split": h.cfg.k_split, "n_split": h.cfg.n_split, "n_gpus": world, "backend": "hip:gfx950", "dycore_only": True, "acoustic_only": not (a.tracers or a.remap), "tracers": a.tracers, "remap": bool(a.remap), "fill": fill, "pt": pt_form, "thermodynamics": thermo, "neg_adj": bool(a.neg_adj), "finite": ok,
+                             "k_split": h.cfg.k_split, "n_split": h.cfg.n_split, "n_gpus": world, "backend": "hip:gfx950", "dycore_only": True, "acoustic_only": not (a.tracers or a.remap), "tracers": a.tracers, "remap": bool(a.remap), "fill": fill, "pt": pt_form, "thermodynamics": thermo, "neg_adj": bool(a.neg_adj), "sat_adj": sat_adj, "finite": ok,
                              "note": ("a step here is k_split AcousticDynamics calls; the reference's dycore_only mainloop (DynamicalCore.step_dynamics) also runs tracer "
                                       "advection and the Lagrangian-to-Eulerian remap (--tracers N --remap add them): not comparable with the reference's 'mainloop' timer")
                              if not (a.tracers and a.remap) else
                              "a step is k_split x [AcousticDynamics, tracer advection, vertical remap] = the body of DynamicalCore.step_dynamics without physics and "
-                             + (("the saturation adjustment (q_con and cappa follow the six water species: moist_cv" + ("; neg_adj3 fixes negative species)" if a.neg_adj else "; neg_adj3 is left out: --neg-adj)"))
+                             + ((("the energy fixer (fv_sat_adj runs inside every remap; q_con and cappa follow" if sat_adj else "the saturation adjustment (q_con and cappa follow") + " the six water species: moist_cv" + ("; neg_adj3 fixes negative species)" if a.neg_adj else "; neg_adj3 is left out: --neg-adj)"))
                                 if a.moist else "moist thermodynamics")},
                    # the reference collector's layout: times.<timer> = {hits, times[rank][step]}; "mainloop" only when the step is the
                    # whole body of step_dynamics (--tracers N --remap), then .jenkins/print_performance_number.py runs on this file as is
                    "times": report,
                    "times_note": ("only the outer clock ('" + loop_name + "') synchronises the device; the nested clocks (DynCore / TracerAdvection / Remapping) are host-side "
-                                  "enqueue intervals. " + (("'mainloop' here = the body of step_dynamics with moist_cv of six water species" + (" and neg_adj3" if a.neg_adj else "") + ": no saturation adjustment, " + ("" if a.neg_adj else "no neg_adj3, ") + "no physics coupling "
+                                  "enqueue intervals. " + (("'mainloop' here = the body of step_dynamics with moist_cv of six water species" + (" and neg_adj3" if a.neg_adj else "") + (" and fv_sat_adj inside every remap: " if sat_adj else ": no saturation adjustment, ") + ("" if a.neg_adj else "no neg_adj3, ") + "no physics coupling "
                                                             "-- the reference's mainloop does more per step." if a.moist else
                                                             "'mainloop' here = the dry body of step_dynamics with N synthetic tracers: no moist thermodynamics, no physics coupling "
                                                             "-- the reference's mainloop does more per step.") if full_step else "")),

@@ -7,7 +7,8 @@ The contract of the call is the reference's: ``state.pt`` holds the temperature 
    rebuilds ``pkz``,
 2. ``k_split`` times: the ``dp1`` copy, :class:`~pace_amd.dyn_core.AcousticDynamics` ("DynCore"), the tracer halo update and
    :class:`~pace_amd.stencils.TracerAdvection` ("TracerAdvection"), :class:`~pace_amd.stencils.LagrangianToEulerian` with the
-   vertical filling where ``config.fill`` asks for it ("Remapping") -- the sequence of ``DycoreHarness.step``,
+   vertical filling where ``config.fill`` asks for it and the saturation adjustment where ``saturation_adjustment`` does
+   ("Remapping") -- the sequence of ``DycoreHarness.step``,
 3. :class:`~pace_amd.stencils.PotentialToTemperature` takes ``pt`` back to K with the ``pkz`` the last remap left, diagnoses
    ``state.omga = delp / delz * w`` and the surface pressure ``DynamicalCore.ps``,
 4. :class:`~pace_amd.stencils.AdjustNegativeTracerMixingRatio`, where asked (``adjust_negative_water``; "NegAdj3"): FV3's
@@ -18,8 +19,9 @@ Without ``water_species`` ``q_con`` and ``cappa`` are fields of the state that t
 the six water species by FV3's ``moist_cv`` where FV3 derives them: step 1 becomes the moist preamble
 (``fv3_pt_from_temperature_moist``: ``q_con``, ``cappa`` from the species, then the conversion) and the remap of step 2 the moist remap
 (``fv3_remap_moist``: remap, fill, ``q_con`` / ``cappa`` from the remapped and filled species, ``pkz`` with the new ``cappa``); step 3 is
-unchanged and reads the ``q_con`` the last remap wrote.  The saturation adjustment, the energy fixer and the physics coupling are
-outside this build.  Every buffer (``dp1``, ``ps``, the operators' own) is allocated by the
+unchanged and reads the ``q_con`` the last remap wrote.  With ``saturation_adjustment`` every remap of step 2 is the adjusting one
+(``fv3_remap_moist_sat``: FV3's ``fv_sat_adj`` between the fill and ``moist_cv``, with ``mdt = timestep / k_split`` and its second pass
+to full saturation in the last remap of the step).  The energy fixer and the physics coupling are outside this build.  Every buffer (``dp1``, ``ps``, the operators' own) is allocated by the
 constructor; ``step_dynamics`` allocates nothing.
 """
 from __future__ import annotations
@@ -52,6 +54,8 @@ class DynamicalCore:
         cubed_to_latlon: bool = True,
         water_species: Optional[Dict[str, str]] = None,
         adjust_negative_water: bool = False,
+        saturation_adjustment: bool = False,
+        sat_adjust_config: Optional[st.SatAdjustConfig] = None,
     ):
         """Arguments as the reference's call.  ``comm``: a :class:`pace_amd.halo.Layout` (None: every rank in this process);
         ``timestep``: the model step ``dt_atmos`` in seconds or as a ``timedelta`` (None: ``config.dt_atmos``); ``tracers``:
@@ -62,7 +66,9 @@ class DynamicalCore:
         field of zeros; ``qvapor`` is required and becomes ``vapor``) -- ``q_con`` and ``cappa`` are then derived from these tracers
         (``moist_cv``) in the preamble and in every remap; None: they are the state's fields as the caller left them;
         ``adjust_negative_water``: run ``neg_adj3`` on ``state.pt`` and the species after the conversion back to temperature (FV3 does
-        whenever ``nwat == 6``); it needs ``water_species`` with all six roles."""
+        whenever ``nwat == 6``); it needs ``water_species`` with all six roles; ``saturation_adjustment``: run FV3's ``fv_sat_adj`` inside
+        every remap (the namelist's ``do_sat_adj``; ``sat_adjust_config``: its parameters, None: FV3's defaults); it needs
+        ``water_species`` with all six roles."""
         sf = stencil_factory
         qf = quantity_factory or sf.quantity_factory
         self.sf, self.qf = sf, qf
@@ -102,6 +108,12 @@ class DynamicalCore:
             if missing:
                 raise ValueError(f"adjust_negative_water=True needs water_species with all six roles (missing: {', '.join(missing)})")
             self.adjust_negative_water = st.AdjustNegativeTracerMixingRatio(sf, qf, grid_data)
+        self.saturation_adjustment = None
+        if saturation_adjustment:
+            missing = [r for r in st.WATER_ROLES if r not in (water_species or {})]
+            if missing:
+                raise ValueError(f"saturation_adjustment=True needs water_species with all six roles (missing: {', '.join(missing)})")
+            self.saturation_adjustment = st.SaturationAdjustment(sf, qf, grid_data, sat_adjust_config)
 
     @property
     def qvapor(self) -> Optional[Quantity]:
@@ -129,7 +141,11 @@ class DynamicalCore:
                     self._tracer_halo.update()
                     self.tracer_advection(tracers, self.dp1, s.mfxd, s.mfyd, s.cxd, s.cyd)
             with timer.clock("Remapping"):
-                self.remap(tracers, s.pt, s.delp, s.delz, s.peln, s.pe, s.pk, s.pkz, s.u, s.v, s.w, s.cappa, self.ps, dyn._wsd, q_con=s.q_con, water=water)
+                if self.saturation_adjustment is not None:
+                    self.remap(tracers, s.pt, s.delp, s.delz, s.peln, s.pe, s.pk, s.pkz, s.u, s.v, s.w, s.cappa, self.ps, dyn._wsd, q_con=s.q_con, water=water,
+                               sat_adjust=self.saturation_adjustment, mdt=dt, last_step=(k == k_split - 1))
+                else:
+                    self.remap(tracers, s.pt, s.delp, s.delz, s.peln, s.pe, s.pk, s.pkz, s.u, s.v, s.w, s.cappa, self.ps, dyn._wsd, q_con=s.q_con, water=water)
         # the last-step conversion of the remap: pkz is the one the remap has just formed with these delp, delz and T_v
         self.potential_to_temperature(s.pt, s.pkz, s.delp, s.delz, s.q_con, s.cappa, s.w, s.pe, qvapor=qv, omga=s.omga, ps=self.ps, recompute_pkz=False)
         if self.adjust_negative_water is not None:

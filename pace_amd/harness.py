@@ -81,6 +81,8 @@ class DycoreHarness:
         vapor: Optional[str] = None,
         moist: bool = False,
         neg_adj: bool = False,
+        sat_adj: bool = False,
+        sat_adjust_config=None,
         _testing_token=None,
     ):
         if fill and not remap:
@@ -93,7 +95,10 @@ class DycoreHarness:
             raise ValueError("moist=True needs temperature=True: moist_cv sits in the preamble and the remap of DynamicalCore.step_dynamics")
         if neg_adj and not moist:
             raise ValueError("neg_adj=True needs moist=True: neg_adj3 works on the six water species of the moist step")
+        if sat_adj and not moist:
+            raise ValueError("sat_adj=True needs moist=True: the saturation adjustment works on the six water species of the moist step")
         self.neg_adj = bool(neg_adj)
+        self.sat_adj, self.sat_adjust_config = bool(sat_adj), sat_adjust_config
         if moist:
             if vapor not in (None, "qvapor"):
                 raise ValueError(f"moist=True: the specific humidity is the species qvapor (vapor={vapor!r})")
@@ -235,7 +240,8 @@ class DycoreHarness:
 
         self.dycore = DynamicalCore(self.layout, self.grids, self.sf, self.sf.quantity_factory, None, self.cfg, self.cfg.dt_atmos, self.state.phis, self.state,
                                     tracers=self.tracers, hord_tr=hord_tr, vapor=vapor, cubed_to_latlon=latlon_winds,
-                                    water_species={n: n for n in WATER_NAMES} if self.moist else None, adjust_negative_water=self.neg_adj)
+                                    water_species={n: n for n in WATER_NAMES} if self.moist else None, adjust_negative_water=self.neg_adj,
+                                    saturation_adjustment=self.sat_adj, sat_adjust_config=self.sat_adjust_config)
         d = self.dycore
         self.dyn = d.acoustic_dynamics
         if not self.layout.loopback:

@@ -118,6 +118,14 @@ class fv3_latent(C.Structure):
     _fields_ = [(n, C.c_double) for n in "hlv hlf t_ice".split()]
 
 
+SAT_PARAMS = "tau_i2s tau_v2l tau_l2v tau_imlt tau_r2g tau_smlt tau_l2r ql_gen qi_gen qi_lim ql_mlt qs_mlt ql0_max qi0_max sat_adj0 t_sub".split()
+SAT_NTAB = 2621  # entries of one saturation table (fv3_sat_adj_tables returns four)
+
+
+class fv3_sat_params(C.Structure):
+    _fields_ = [(n, C.c_double) for n in SAT_PARAMS]
+
+
 _D = C.c_double
 _I = C.c_int
 _S = C.c_void_p  # stream
@@ -182,6 +190,10 @@ _PROTOS = {
     "fv3_pt_from_temperature_moist": (C.c_int, [C.c_void_p] + [F] * 6 + [P(fv3_water), _S]),
     "fv3_remap_moist": (C.c_int, [C.c_void_p, _I, P(F)] + [F] * 14 + [P(fv3_water), _I, _S]),
     "fv3_neg_adj3": (C.c_int, [C.c_void_p, P(fv3_water), P(fv3_latent), F, F, _S]),
+    "fv3_sat_adj": (C.c_int, [C.c_void_p, P(fv3_water), P(fv3_latent), P(fv3_sat_params)] + [F] * 6 + [_D, _I, _S]),
+    "fv3_sat_adj_level0": (C.c_int, [C.c_void_p, P(C.c_int)]),
+    "fv3_sat_adj_tables": (C.c_int, [C.c_void_p, P(C.c_double), C.c_long]),
+    "fv3_remap_moist_sat": (C.c_int, [C.c_void_p, _I, P(F)] + [F] * 14 + [P(fv3_water), _I, P(fv3_latent), P(fv3_sat_params), _D, _I, _S]),
     "fv3_cubed_to_latlon": (C.c_int, [C.c_void_p, _I] + [F] * 8 + [_S]),
     "fv3_diag_pack": (C.c_int, [C.c_void_p, F, _I, _I, _I, _I, C.c_void_p, C.c_long, _S]),
     "fv3_diag_column_integral": (C.c_int, [C.c_void_p, F, F, C.c_void_p, C.c_long, _S]),

@@ -7,8 +7,10 @@ call time [REF tests/main/fv3core/test_dycore_call.py:193-211].
 """
 from __future__ import annotations
 
+import dataclasses
 from typing import Optional
 
+from .constants import SAT_ADJ_DEFAULTS as _SAT
 from .constants import X_DIM, X_INTERFACE_DIM, Y_DIM, Y_INTERFACE_DIM, Z_DIM, Z_INTERFACE_DIM
 from .context import StencilFactory
 from .quantity import Quantity
@@ -285,20 +287,35 @@ class LagrangianToEulerian(_Op):
     ``fill`` (the namelist's ``fill``, default off): after the remap the negative tracer means are filled in the vertical
     (:class:`FillNegativeTracerValues` with the Eulerian ``delp``) on the same stream, where the reference runs its ``fillz``.
     ``water`` (a :class:`WaterSpecies` whose species are among ``tracers``) with ``q_con``: the moist remap ``fv3_remap_moist`` --
-    remap, fill, ``q_con`` / ``cappa`` from the filled species (``moist_cv``), ``pkz`` with the new ``cappa``, FV3's order."""
+    remap, fill, ``q_con`` / ``cappa`` from the filled species (``moist_cv``), ``pkz`` with the new ``cappa``, FV3's order.
+    ``sat_adjust`` (a :class:`SaturationAdjustment`; needs ``water`` with all six species and ``mdt``, the remap interval in seconds):
+    ``fv3_remap_moist_sat`` -- the saturation adjustment between the fill and ``moist_cv``, in the same closing kernel; ``last_step``
+    asks for its second pass to full saturation."""
 
     def __init__(self, stencil_factory, quantity_factory=None, grid_data=None, *args, fill: bool = False, **kw):
         super().__init__(stencil_factory, quantity_factory, grid_data, *args, **kw)
         self.fill = bool(fill)
         self._fillz = FillNegativeTracerValues(stencil_factory, quantity_factory, grid_data) if self.fill else None
 
-    def __call__(self, tracers, pt, delp, delz, peln, pe, pk, pkz, u, v, w, cappa, ps, wsd, q_con=None, water=None):
+    def __call__(self, tracers, pt, delp, delz, peln, pe, pk, pkz, u, v, w, cappa, ps, wsd, q_con=None, water=None, *, sat_adjust=None, mdt=None, last_step=False):
         import ctypes as C
 
         from . import lib as _lib
 
         qs = list(tracers.values()) if tracers else []
         arr = (_lib.F * max(len(qs), 1))(*[C.pointer(q.field) for q in qs])
+        if sat_adjust is not None:
+            # (sat_adjust: a SaturationAdjustment) FV3's order with do_sat_adj: remap, fill, fv_sat_adj, moist_cv, pkz -- all inside the entry
+            if water is None or q_con is None:
+                raise ValueError("LagrangianToEulerian: sat_adjust needs water and q_con (the adjustment works on the six water species)")
+            if mdt is None:
+                raise ValueError("LagrangianToEulerian: sat_adjust needs mdt (the remap interval in seconds)")
+            st = self.sf.lib.fv3_remap_moist_sat(self.sf.ctx, len(qs), arr, pt.fref, delp.fref, delz.fref, peln.fref, pe.fref, pk.fref, pkz.fref, u.fref, v.fref, w.fref,
+                                                 cappa.fref, q_con.fref, ps.fref, wsd.fref, water.cref, 1 if self.fill else 0, sat_adjust.latent_ref, sat_adjust.params_ref,
+                                                 float(mdt), 1 if last_step else 0, self.sf.stream_handle)
+            if st != 0:
+                raise _lib.Fv3Error(f"fv3_remap_moist_sat failed ({st}): " + self.sf.lib.fv3_last_error(self.sf.ctx).decode())
+            return
         if water is not None:
             # FV3's order: remap, fill, moist_cv from the filled species, pkz with the new cappa -- all inside the entry
             if q_con is None:
@@ -412,6 +429,88 @@ class AdjustNegativeTracerMixingRatio(_Op):
         st = sf.lib.fv3_neg_adj3(sf.ctx, water.cref, self._lref, pt.fref, delp.fref, sf.stream_handle)
         if st != 0:
             raise _lib.Fv3Error(f"fv3_neg_adj3 failed ({st}): " + sf.lib.fv3_last_error(sf.ctx).decode())
+
+
+@dataclasses.dataclass
+class SatAdjustConfig:
+    """The namelist parameters of the saturation adjustment (``fv3_sat_params`` in include/fv3_mi355x.h); the field names are the
+    yaml keys of ``dycore_config``, the defaults FV3's (``pace_amd.constants.SAT_ADJ_DEFAULTS``)."""
+
+    tau_i2s: float = _SAT["tau_i2s"]
+    tau_v2l: float = _SAT["tau_v2l"]
+    tau_l2v: float = _SAT["tau_l2v"]
+    tau_imlt: float = _SAT["tau_imlt"]
+    tau_r2g: float = _SAT["tau_r2g"]
+    tau_smlt: float = _SAT["tau_smlt"]
+    tau_l2r: float = _SAT["tau_l2r"]
+    ql_gen: float = _SAT["ql_gen"]
+    qi_gen: float = _SAT["qi_gen"]
+    qi_lim: float = _SAT["qi_lim"]
+    ql_mlt: float = _SAT["ql_mlt"]
+    qs_mlt: float = _SAT["qs_mlt"]
+    ql0_max: float = _SAT["ql0_max"]
+    qi0_max: float = _SAT["qi0_max"]
+    sat_adj0: float = _SAT["sat_adj0"]
+    t_sub: float = _SAT["t_sub"]
+
+
+class SaturationAdjustment(_Op):
+    """``fv_sat_adj`` (FV3 ``fv_cmp.F90``, the non-hydrostatic form; pyFV3 ``SatAdjust3d``), which the remap runs when ``do_sat_adj`` is
+    set: phase changes between the six water species with the latent heat booked on the temperature (``fv3_sat_adj`` in
+    include/fv3_mi355x.h holds the algorithm).  Call as ``(water, tv, delp, delz, q_con, cappa, pkz, mdt, last_step=False)``: in place
+    on the compute cells of the levels below 10 hPa (``level0`` is the first); ``tv`` is ``T (1 + zvir qv)(1 - q_con)`` in and out,
+    ``q_con``, ``cappa`` and ``pkz`` are written, ``delp`` and ``delz`` only read; ``mdt``: the remap interval in seconds;
+    ``last_step``: the second pass to full saturation.  Handed to :class:`LagrangianToEulerian` as ``sat_adjust=`` it runs inside
+    the moist remap (``fv3_remap_moist_sat``).  Not built: the energy fixer, the ``out_dt`` tendency, the cloud fraction."""
+
+    def __init__(self, stencil_factory, quantity_factory=None, grid_data=None, config=None, *, hydrostatic=False, do_qa=False, hlv=None, hlf=None, t_ice=None):
+        import ctypes as C
+
+        from . import constants as _c
+        from . import lib as _lib
+
+        super().__init__(stencil_factory, quantity_factory, grid_data)
+        if hydrostatic:
+            raise NotImplementedError("SaturationAdjustment: only the non-hydrostatic form of fv_sat_adj is built")
+        if do_qa:
+            raise NotImplementedError("SaturationAdjustment: the cloud fraction of fv_sat_adj (do_qa) is not built")
+        self.config = config or SatAdjustConfig()
+        self.latent = _lib.fv3_latent(float(_c.HLV if hlv is None else hlv), float(_c.HLF if hlf is None else hlf), float(_c.T_ICE if t_ice is None else t_ice))
+        self.params = _lib.fv3_sat_params(*[float(getattr(self.config, n)) for n in _lib.SAT_PARAMS])
+        self.latent_ref, self.params_ref = C.byref(self.latent), C.byref(self.params)
+
+    @property
+    def level0(self) -> int:
+        import ctypes as C
+
+        k = C.c_int()
+        _lib_check(self.sf, self.sf.lib.fv3_sat_adj_level0(self.sf.ctx, C.byref(k)), "fv3_sat_adj_level0")
+        return k.value
+
+    def tables(self):
+        """(4, 2621) float64: tablew, table2, desw, des2 as the kernels hold them (after the context's first adjusting call)."""
+        import ctypes as C
+
+        import numpy as np
+
+        from . import lib as _lib
+
+        out = np.empty((4, _lib.SAT_NTAB), dtype=np.float64)
+        _lib_check(self.sf, self.sf.lib.fv3_sat_adj_tables(self.sf.ctx, out.ctypes.data_as(C.POINTER(C.c_double)), out.size), "fv3_sat_adj_tables")
+        return out
+
+    def __call__(self, water, tv, delp, delz, q_con, cappa, pkz, mdt, last_step=False):
+        sf = self.sf
+        st = sf.lib.fv3_sat_adj(sf.ctx, water.cref, self.latent_ref, self.params_ref, tv.fref, delp.fref, delz.fref, q_con.fref, cappa.fref, pkz.fref, float(mdt),
+                                1 if last_step else 0, sf.stream_handle)
+        _lib_check(sf, st, "fv3_sat_adj")
+
+
+def _lib_check(sf, st, what):
+    from . import lib as _lib
+
+    if st != 0:
+        raise _lib.Fv3Error(f"{what} failed ({st}): " + sf.lib.fv3_last_error(sf.ctx).decode())
 
 
 class TemperatureToPotential(_Op):
