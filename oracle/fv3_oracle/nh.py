@@ -19,7 +19,7 @@ from .util import Dom, alt, copy_corners, fill_4corners
 # default); counting never changes a value.
 _COUNTS = None
 COUNTERS = ("sim1_floor", "sim1_free", "dzc_limited", "dzc_free", "dzd_limited", "dzd_free", "dzc_upwind_pos_x", "dzc_upwind_neg_x", "dzc_upwind_pos_y",
-            "dzc_upwind_neg_y", "heat_limited", "heat_free", "ray_damped", "ray_nudged_only", "ray_none")
+            "dzc_upwind_neg_y", "dzd_damped", "dzd_undamped", "heat_limited", "heat_free", "ray_damped", "ray_nudged_only", "ray_none")
 
 
 def enable_counters(on: bool = True) -> None:
@@ -35,7 +35,8 @@ def reset_counters() -> None:
 def counters():
     """Counts since the last reset: sim1_solver -- levels whose new thickness took the p_fac pressure floor / did not; update_dz_c /
     update_dz_d -- interface heights the dz_min scan raised / left; update_dz_c -- interface fluxes that took the upwind value from
-    the cell behind (flux > 0) / ahead, in x and in y; apply_diffusive_heating -- cells whose temperature change was cut to the
+    the cell behind (flux > 0) / ahead, in x and in y; update_dz_d -- interfaces (per call) whose heights get the del-n damping
+    (damp_vt > 1e-5) / do not; apply_diffusive_heating -- cells whose temperature change was cut to the
     limit / was not; ray_fast -- levels (per call) that are damped / only receive the momentum fix / neither."""
     return dict(_COUNTS or dict.fromkeys(COUNTERS, 0))
 
@@ -66,7 +67,7 @@ def update_dz_c(D: Dom, dp_ref, zs, ut, vt, gz, ws, dt):
     bot_ratio = dp_ref[nz - 1] / (dp_ref[nz - 2] + dp_ref[nz - 1])
     Rx = S(is_ - 1, ie + 2, js - 1, je + 1)
     Ry = S(is_ - 1, ie + 1, js - 1, je + 2)
-    xfx = np.zeros((gz.shape[0], gz.shape[1], nz + 1))
+    xfx = np.zeros((gz.shape[0], gz.shape[1], nz + 1), dtype=gz.dtype)
     yfx = np.zeros_like(xfx)
     for a, src, R in ((xfx, ut, Rx), (yfx, vt, Ry)):
         s = src[R]
@@ -102,10 +103,11 @@ def update_dz_c(D: Dom, dp_ref, zs, ut, vt, gz, ws, dt):
 # ---------------------------------------------------------------------------
 def edge_profile(q, dp0):
     """Layer means -> interface values by the cubic-spline-like profile of FV3 ``edge_profile``
-    (limiter 0).  q: [..., nz] -> [..., nz+1]."""
+    (limiter 0).  q: [..., nz] -> [..., nz+1].  The work arrays and the level ratios take the dtype of q."""
     nz = q.shape[-1]
-    qe = np.zeros(q.shape[:-1] + (nz + 1,))
-    gam = np.zeros(nz + 1)
+    dp0 = np.asarray(dp0, dtype=q.dtype)
+    qe = np.zeros(q.shape[:-1] + (nz + 1,), dtype=q.dtype)
+    gam = np.zeros(nz + 1, dtype=q.dtype)
     g0 = dp0[1] / dp0[0]
     xt1 = 2.0 * g0 * (g0 + 1.0)
     bet = g0 * (g0 + 0.5)
@@ -138,24 +140,22 @@ def update_dz_d(D: Dom, cfg, col, dp_ref, zs, zh, crx, cry, xfx, yfx, ws, dt):
     dz_min = D.c.DZ_MIN
     damp = np.append(col["damp_vt"], col["damp_vt"][-1])
     ndif = np.append(col["nord_v"], col["nord_v"][-1]).astype(int)
-
-
     damp_on = damp.copy()  # (the switch "is this interface damped" is the raw coefficient in both forms)
     if alt("dz_damp_scaled"):  # FV3_ALT=dz_damp_scaled: the coefficient d_sw's vorticity damping uses
         damp = (damp * D.grid.da_min_c) ** (ndif + 1)
     shp = zh.shape[:2] + (nz + 1,)
-    crx_adv = np.zeros(shp)
-    xfx_adv = np.zeros(shp)
-    cry_adv = np.zeros(shp)
-    yfx_adv = np.zeros(shp)
+    crx_adv = np.zeros(shp, dtype=zh.dtype)
+    xfx_adv = np.zeros(shp, dtype=zh.dtype)
+    cry_adv = np.zeros(shp, dtype=zh.dtype)
+    yfx_adv = np.zeros(shp, dtype=zh.dtype)
     Rx = S(is_, ie + 1, jsd, jed)
     Ry = S(isd, ied, js, je + 1)
     crx_adv[Rx] = edge_profile(crx[Rx][:, :, :nz], dp_ref)
     xfx_adv[Rx] = edge_profile(xfx[Rx][:, :, :nz], dp_ref)
     cry_adv[Ry] = edge_profile(cry[Ry][:, :, :nz], dp_ref)
     yfx_adv[Ry] = edge_profile(yfx[Ry][:, :, :nz], dp_ref)
-    ra_x = np.zeros(shp)
-    ra_y = np.zeros(shp)
+    ra_x = np.zeros(shp, dtype=zh.dtype)
+    ra_y = np.zeros(shp, dtype=zh.dtype)
     R = S(is_, ie, jsd, jed)
     ra_x[R] = m.area[R] + xfx_adv[R] - xfx_adv[S(is_ + 1, ie + 1, jsd, jed)]
     R = S(isd, ied, js, je)
@@ -171,6 +171,8 @@ def update_dz_d(D: Dom, cfg, col, dp_ref, zs, zh, crx, cry, xfx, yfx, ws, dt):
             z2 = zh[:, :, ks].copy()
             fx, fy = fv_tp_2d(D, z2, crx_adv[:, :, ks], cry_adv[:, :, ks], xfx_adv[:, :, ks], yfx_adv[:, :, ks], ra_x[:, :, ks], ra_y[:, :, ks], cfg.hord_tm)
             new = (z2[Rc] * m.area[Rc] + fx[Rc] - fx[Rcx] + fy[Rc] - fy[Rcy]) / (ra_x[:, :, ks][Rc] + ra_y[:, :, ks][Rc] - m.area[Rc])
+            if _COUNTS is not None:
+                _COUNTS["dzd_damped" if damp_on[k0] > 1.0e-5 else "dzd_undamped"] += k - k0
             if damp_on[k0] > 1.0e-5:
                 fx2, fy2, _ = del6_vt_flux(D, int(ndif[k0]), float(damp[k0]), z2)
                 new = new + (fx2[Rc] - fx2[Rcx] + fy2[Rc] - fy2[Rcy]) * m.rarea[Rc]

@@ -83,6 +83,9 @@ PLANS = {
     "nh_p_grad": ("nh_p_grad", [F(0), F(1), F(2), F(3), F(4), F(5), S(6), S(7), S(8)], [("u", 0, U, 0, "nz"), ("v", 1, V, 0, "nz")]),
     "apply_diffusive_heating": ("apply_diffusive_heating", [F(0), F(1), F(2), F(3), F(4), S(5)], [("pt", 4, CELLS, 0, "nz")]),
     "ray_fast": ("ray_fast", [F(1), F(2), F(3), S(6), S(7)], [("u", 1, U, 0, "nz"), ("v", 2, V, 0, "nz"), ("w", 3, CELLS, 0, "nz")]),
+    # (tests/test_height_pgf_operator_edges.py; ("i", n) = integer argument)
+    "p_grad_c": ("p_grad_c", [F(2), F(3), F(4), F(5), F(6), S(7)], [("uc", 2, V, 0, "nz"), ("vc", 3, U, 0, "nz")]),
+    "del2_cubed": ("del2_cubed", [F(0), S(1), ("i", 2)], [("heat_source", 0, CELLS, 0, "nz")]),
 }
 # the tolerances of test_operator_parity.py (test_update_dz_c, test_riem_solver_c, test_update_dz_d, test_riem_solver3_on_recorded_inputs,
 # test_pk3_halo_and_edge_pe, test_nh_p_grad, test_ray_fast, test_del2_cubed_and_diffusive_heating)
@@ -96,6 +99,8 @@ TOL = {
     "nh_p_grad": {"u": 1e-12, "v": 1e-12},
     "apply_diffusive_heating": {"pt": 1e-14},
     "ray_fast": {"u": 1e-13, "v": 1e-13, "w": 1e-13},
+    "p_grad_c": {"uc": 1e-13, "vc": 1e-13},
+    "del2_cubed": {"heat_source": 1e-12},
 }
 # fp32 build against the fp64 oracle: 2 x the worst measured error (module docstring), per state and operator
 TOL32 = {
@@ -194,7 +199,7 @@ def replay(dv, name, cl):
             call_args.append(qs[i].fref)
         else:
             v = cl[0]["ins"][i]
-            call_args.append(int(bool(v)) if kind == "b" else float(v))
+            call_args.append(int(bool(v)) if kind == "b" else int(v) if kind == "i" else float(v))
     dv.sf.call(entry, *call_args)
     if dv.sf.backend != "hostemu":
         torch.cuda.synchronize()
