@@ -342,7 +342,7 @@ int fv3_gather_run_jobs(fv3_ctx *c, const fv3_gather_job *jobs, int n, void *str
 // the auxiliary stream is off or in the host emulation -- everything then runs in program order).
 // fv3_signal(c, from, e) / fv3_wait(c, to, e): event e recorded on `from`, later awaited by `to`.
 // ---------------------------------------------------------------------------------------------
-fv3_stream_t fv3_aux(fv3_ctx *c, fv3_stream_t s);
+fv3_stream_t fv3_aux(const fv3_ctx *c, fv3_stream_t s);
 void fv3_signal(fv3_ctx *c, fv3_stream_t from, int e);
 void fv3_wait(fv3_ctx *c, fv3_stream_t to, int e);
 

@@ -353,7 +353,7 @@ static void csw_fused_stream(fv3_ctx *c, fv3_stream_t s, const Real *u, const Re
     const int k = live ? k_ : nk - 1;
     // Round 6 (uava_thin: inside the sequencer, not the last sub-step of a call): ua / va of this level are stored in full only where d_sw reads them (no damping
     // chain on the level); elsewhere only the two cells next to the rectangle's boundary, which the boundary-window kernels read -- two field writes less.
-    const bool sua = !uava_thin || nord_tab[k] == 0;
+    const bool sua = !uava_thin || fv3_level_reads_uava(nord_tab, k);
     const int tby = tile / nstrip, tbx = tile - tby * nstrip;
     const CswRect rc = csw_rect(gp->flags[t], nx, ny, npx, npy);
     const int c0 = rc.i_lo + tbx * CSWF_OUT;
@@ -737,8 +737,8 @@ extern "C" int fv3_c_sw(fv3_ctx *c, const fv3_field *delp_, const fv3_field *pt_
   static const bool win_overlap = fv3_sw(FV3SW_CSW_WIN_OVERLAP);
   fv3_stream_t sw_ = (fused && b_split && win_overlap) ? fv3_aux(c, s) : s;
   if (sw_ != s) {
-    fv3_signal(c, s, 0);
-    fv3_wait(c, sw_, 0);
+    fv3_signal(c, s, EV_FORK);
+    fv3_wait(c, sw_, EV_FORK);
   }
   if (b_split) {
     // the four windows along the sub-domain boundary (launch_frame: W / E as narrow 8 x 32 workgroups, S / N as they lie)
@@ -961,8 +961,8 @@ extern "C" int fv3_c_sw(fv3_ctx *c, const fv3_field *delp_, const fv3_field *pt_
     }
   }
   if (sw_ != s) {
-    fv3_signal(c, sw_, 1);
-    fv3_wait(c, s, 1);
+    fv3_signal(c, sw_, EV_WIN_JOIN);
+    fv3_wait(c, s, EV_WIN_JOIN);
   }
 
   // the in-place corner fixes of ua / va the reference leaves behind (checkpointed as uad / vad)
@@ -1160,8 +1160,8 @@ extern "C" int fv3_c_sw(fv3_ctx *c, const fv3_field *delp_, const fv3_field *pt_
   static const bool defer_on = fv3_sw(FV3SW_CSW_DEFER);
   fv3_stream_t sd_ = (fused && defer_on && c->seq.csw_defer) ? fv3_aux(c, s) : s;
   if (sd_ != s) {
-    fv3_signal(c, s, 6);
-    fv3_wait(c, sd_, 6);
+    fv3_signal(c, s, EV_CSW_LATE_FORK);
+    fv3_wait(c, sd_, EV_CSW_LATE_FORK);
   }
   if (fused) {  // the four windows along the sub-domain boundary
     const int e0 = g.nx - 4;
@@ -1213,7 +1213,7 @@ extern "C" int fv3_c_sw(fv3_ctx *c, const fv3_field *delp_, const fv3_field *pt_
     }
   }
   if (sd_ != s) {
-    fv3_signal(c, sd_, 7);
+    fv3_signal(c, sd_, EV_CSW_LATE_JOIN);
     c->csw_pending = true;  // (the sequencer joins: fv3_csw_join)
   }
   return fv3_post(c, s, "c_sw");
@@ -1222,7 +1222,7 @@ extern "C" int fv3_c_sw(fv3_ctx *c, const fv3_field *delp_, const fv3_field *pt_
 // the join c_sw left to the sequencer (seq.csw_defer): the caller's stream waits for the stage D / E windows on the auxiliary stream
 int fv3_csw_join(fv3_ctx *c, void *stream) {
   if (c && c->csw_pending) {
-    fv3_wait(c, (fv3_stream_t)stream, 7);
+    fv3_wait(c, (fv3_stream_t)stream, EV_CSW_LATE_JOIN);
     c->csw_pending = false;
   }
   return FV3_OK;

@@ -449,7 +449,7 @@ int fv3_ctx_create(fv3_ctx **out, const fv3_gridspec *spec, const fv3_griddata *
 }
 
 extern "C++" {
-fv3_stream_t fv3_aux(fv3_ctx *c, fv3_stream_t s) {
+fv3_stream_t fv3_aux(const fv3_ctx *c, fv3_stream_t s) {
 #ifdef FV3_HOST_EMU
   (void)c;
   return s;

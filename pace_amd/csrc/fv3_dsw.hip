@@ -890,13 +890,155 @@ static void divdamp_patches(fv3_ctx *c, fv3_stream_t s, const Real *divgd, Real 
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// d_sw: plan, stages, streams.  dsw_plan() takes EVERY decision of one call before its first launch -- from the context's host tables, the sequencer's hints
+// (c->seq), the switch table (the LIVE rows read once per call, here) and whether an auxiliary stream exists -- and launches nothing.  The stages further down
+// take the plan by const reference and decide nothing; fv3_d_sw_out strings them together.  Scratch slots: the table at DswScratch; events: fv3_event (fv3_ops.h).
+// ---------------------------------------------------------------------------------------------------------------------------
+struct DswPlan {
+  bool oop, debug;   // new scalars beside the old ones (fv3_d_sw_out's o_*); FV3_DEBUG_FD
+  const char *fail;  // non-null: the sequencer's hints ask for a form this configuration does not run
+  // streams: the caller's | the auxiliary one (== s: none) | the wind stages' (s_aux with wind_overlap) | the staged wind levels' (s_aux when forked) | the chainless
+  // vorticity levels' transport
+  fv3_stream_t s, s_aux, s_wind, s_sponge, s_vort_low;
+  int nord_max_v, nord_max_w, nord_max_t, nord_max;
+  // scalars.  fused_scalars: fxadv + the marches of fv3_tp4.hip (FV3_DSW_SCALARS=separate: the four transports as four launches + the division kernel, round-1 form,
+  // A/B reference); scalars_mode: dsw_scalars_stream's (0 = quad).  Levels from fd_k0 on (every chain switched on and of order 2: all but the sponge layers) run the
+  // del-n chains INSIDE the marches (fv3_tp4.hip, FD) and only the faces on the cube-corner patches are computed for them; FV3_DSW_DELN=arrays: the chains of every
+  // level as del6_stream launches (round-2 form, A/B reference).  split_levels: dsw_scalars_stream puts the sponge layers on s_aux.
+  // acc_defer: deferred accumulation of the Courant numbers (fv3_step.hip): cx / cy are not touched by fxadv; crx / cry are this sub-step's own arrays
+  bool fused_scalars, split_levels, acc_defer;
+  int scalars_mode, fd_k0;
+  // wind.  keep_uv_dx: levels that form the damping heat (d_con > 1e-5) WITHOUT vorticity damping (damp_vt <= 1e-5) read the pre-update u*dx / v*dy where the
+  // damping fluxes would be (the work arrays keep those values in the reference's data flow); only non-default configs (do_vort_damp off / vtdm4 = 0) have such levels.
+  // Levels from fdw_k0 on (vorticity damping of order 2: all but the sponge layers): the vorticity transport loads wk and adds f0 itself and runs wk's del-n chain
+  // inside its march (tp2d TF_WIND | TF_FD) -- no absolute-vorticity field, no del6_stream launch over those levels but for the tile-edge strips.
+  // FV3_DSW_VORT_DELN=arrays: the round-2 form (A/B reference).  heat_in_march: the vorticity march forms the damping heat there (FV3_DSW_HEAT=separate: not).
+  // vort_in_ke: round 5, FV3_DSW_VORT_IN_KE=1 (experiment R5-30, off by default): the corner-KE march, which reads u and v anyway, forms the vorticity of the cells
+  // under its corners -- columns 4 .. nx - 2, rows 3 .. ny - 3 at least -- and the vorticity launch only serves the four windows of the frame around them (sub-domains
+  // without a tile edge on a side get those cells from both: the same values).  Same bits; measured neutral: the launch goes from 1.61 to 0.25 ms, the march from
+  // 3.00 to 4.15 (23 more registers at four waves per SIMD, three more metric rows, one more store stream).
+  bool keep_uv_dx, heat_separate, heat_in_march, vort_in_ke, ke_staged;
+  // Round 6: levels kfz .. nz - 1 run the FUSED wind stage (fv3_wind.hip: vorticity, corner KE, damping chain, corner interpolation and the damping in one march);
+  // the staged kernels then only serve the levels 0 .. ks1 = kfz - 1 (the sponge layers: no chain, absolute-vorticity field).  FV3_DSW_WINDSTAGE=staged: every level
+  // through the staged kernels (A/B).
+  int fdw_k0, kfz, ks1;
+  // sponge_forked: with the fused stage on every other level, the staged kernels only serve the sponge layers (3 of 79 levels: launches of a few dozen waves, 0.05 -
+  // 0.3 ms each, ~0.8 ms in a row with the gaps between them).  Their whole chain -- vorticity, corner KE, divergence + damping, corner interpolation, the vorticity's
+  // del-n fluxes, the vorticity transport with the wind update -- touches no level the march works on, so it goes to the auxiliary stream and runs BESIDE the fused
+  // stage and the vorticity march (EV_SUB_FORK, EV_STAGED_READY: levels from fdw_k0 on feed the vorticity march, EV_SUB_JOIN after it).  FV3_DSW_SPONGE_WIND=serial:
+  // program order (A/B).
+  // wind_overlap: the wind stages up to the damping coefficient need fxadv's contravariant winds and the D-grid winds, NOT the scalar transports -- and their kernels
+  // are bandwidth-bound thread-per-point / light marching kernels, while the scalar marches are bound by instruction issue at two waves per SIMD.  Round 4,
+  // FV3_DSW_WIND_OVERLAP=1: queued on s_aux behind the sponge-layer launches, beside the scalar marches (default: in program order behind them, the round-3
+  // sequence; same values).  Measured (same box, alternating runs, C768): d_sw 51.6 -> 50.8 ms, but the halo copies that run inside d_sw 1.96 -> 2.5 and the sub-step
+  // 113.6 -> 114.0 ms: the branch takes from the marches what it gains -- one d_sw call moves 252 GB in 51 ms = 4.9 TB/s, i.e. the operator as a whole is at the
+  // bandwidth the chip sustains; overlapping its parts creates no capacity.  Never with keep_uv_dx (the flux slots SC_E / SC_F would be shared with the air-mass fluxes).
+  bool sponge_forked, wind_overlap;
+  // divergence damping.  dd_sep: the marching iteration writes its result beside divgd (dnew_sep: into scratch; else nord_max == 0 and there is none), so the
+  // un-iterated divergence stays readable there and the nord > 0 levels need no copy of it into delpc; then only the levels kd0 .. kd1 that read ua / va
+  // (fv3_level_reads_uava: the sponge layers) have work in the divergence kernel.  keep_divgd: the operator's contract leaves the iterated divergence in divgd
+  // (D_SW-Out carries it).  Inside fv3_acoustic_step nobody reads it: the next c_sw overwrites the workspace field -- the sequencer says so (seq.divgd_dead) and the
+  // copy of the iteration's result into divgd (one field write per call) is skipped when the iteration wrote beside it.
+  bool dd_sep, dnew_sep, keep_divgd;
+  int kd0, kd1;
+  // side_store: the vorticity march's damping-heat epilogue wants copies of the winds on its segment / strip boundaries, made before it updates them in place: the
+  // fused wind stage has every row of u and v in registers, so it stores them (sx_side_copy then only serves the levels under side_from = kfz).  Not beside the
+  // scalar marches (wind_overlap): the arrays hold their new fields then.  FV3_DSW_SIDE=copy: the separate copies (A/B).
+  bool side_store;
+  int side_from, side_seg;
+};
+
+static DswPlan dsw_plan(const fv3_ctx *c, bool out_of_place, fv3_stream_t s) {
+  const Geo &g = c->g;
+  const int nz1 = g.nz - 1;
+  DswPlan p{};
+  p.oop = out_of_place;
+  p.debug = fv3_sw(FV3SW_DEBUG_FD);
+  p.s = s;
+  p.s_aux = fv3_aux(c, s);
+  for (int k = 0; k < g.nz; ++k) {
+    p.nord_max_v = std::max(p.nord_max_v, c->nord_v_h[k]);
+    p.nord_max_w = std::max(p.nord_max_w, c->nord_w_h[k]);
+    p.nord_max_t = std::max(p.nord_max_t, c->nord_t_h[k]);
+    p.nord_max = std::max(p.nord_max, c->nord_h[k]);
+    p.keep_uv_dx = p.keep_uv_dx || (c->d_con_h[k] > 1.0e-5 && !(c->damp_vt_h[k] > 1.0e-5));
+  }
+  const int sc_env = fv3_sw(FV3SW_DSW_SCALARS);  // (0 default, 1 separate, 2 quad)
+  p.fused_scalars = sc_env != 1 && p.nord_max_v <= 2 && p.nord_max_t <= 2 && p.nord_max_w <= 2;
+  p.scalars_mode = sc_env == 2 ? 0 : 1;
+  p.acc_defer = c->seq.acc_defer;
+  if (c->seq.acc_first && !p.fused_scalars) p.fail = "d_sw: the sequencer's first-sub-step form of the accumulators needs the fused scalar marches";
+  else if (p.acc_defer && !p.fused_scalars) p.fail = "d_sw: the sequencer's deferred accumulation needs the fused scalar marches (fxadv with the Courant numbers)";
+  p.fd_k0 = g.nz;
+  if (p.fused_scalars && !fv3_sw_is(FV3SW_DSW_DELN, "arrays") && p.scalars_mode == 1)
+    for (int k = nz1; k >= 0; --k) {
+      const bool all2 = c->nord_v_h[k] == 2 && c->nord_w_h[k] == 2 && c->nord_t_h[k] == 2 && c->damp_vt_h[k] > 1.0e-4 && c->damp_w_h[k] > 1.0e-5 && c->damp_t_h[k] > 1.0e-4;
+      if (!all2) break;
+      p.fd_k0 = k;
+    }
+  p.split_levels = p.fused_scalars && p.s_aux != s && p.scalars_mode == 1 && p.fd_k0 > 0 && p.fd_k0 <= nz1;
+  p.fdw_k0 = g.nz;
+  if (!(fv3_sw_is(FV3SW_DSW_VORT_DELN, "arrays") || fv3_sw_is(FV3SW_TP2D_MODE, "staged") || fv3_sw_is(FV3SW_DEL6_MODE, "staged") || p.keep_uv_dx))
+    for (int k = nz1; k >= 0; --k) {
+      if (!(c->nord_v_h[k] == 2 && c->damp_vt_h[k] > 1.0e-5)) break;
+      p.fdw_k0 = k;
+    }
+  p.heat_separate = fv3_sw_is(FV3SW_DSW_HEAT, "separate");
+  p.heat_in_march = c->cfg.d_con > 1.0e-5 && !p.heat_separate && p.fdw_k0 <= nz1 && tp2d_fd_lean(c, c->cfg.hord_vt, p.fdw_k0, nz1);
+  p.ke_staged = fv3_sw(FV3SW_KE_STAGED);  // (A/B switches for profiling: this and FV3_DIVDAMP_STAGED)
+  const bool dd_staged = fv3_sw(FV3SW_DIVDAMP_STAGED);
+  p.vort_in_ke = fv3_sw(FV3SW_DSW_VORT_IN_KE) && !p.keep_uv_dx && !p.ke_staged && g.nx >= 12 && g.ny >= 12;
+  p.kfz = g.nz;
+  if (!(fv3_sw_is(FV3SW_DSW_WINDSTAGE, "staged") || p.ke_staged || dd_staged || p.keep_uv_dx || p.vort_in_ke || p.nord_max > DD_NMAX || p.nord_max <= 0 || g.nx < 8 || g.ny < 8))
+    for (int k = nz1; k >= p.fdw_k0; --k) {
+      if (!(c->nord_h[k] >= 1 && c->nord_h[k] <= DD_NMAX)) break;
+      p.kfz = k;
+    }
+  p.ks1 = p.kfz - 1;
+  p.wind_overlap = p.fused_scalars && p.s_aux != s && fv3_sw(FV3SW_DSW_WIND_OVERLAP) && !p.keep_uv_dx;
+  p.s_wind = p.wind_overlap ? p.s_aux : s;
+  p.sponge_forked = p.kfz <= nz1 && p.ks1 >= 0 && p.fdw_k0 <= p.kfz && !p.wind_overlap && !fv3_sw_is(FV3SW_DSW_SPONGE_WIND, "serial") && p.s_aux != s;
+  p.s_sponge = p.sponge_forked ? p.s_aux : p.s_wind;
+  p.s_vort_low = p.fdw_k0 > 0 && p.fdw_k0 <= nz1 ? p.s_aux : s;
+  p.dd_sep = !(dd_staged || p.nord_max > DD_NMAX);
+  p.dnew_sep = p.dd_sep && p.nord_max > 0;
+  p.keep_divgd = !(c->seq.divgd_dead && p.dd_sep);
+  p.kd0 = 0;
+  p.kd1 = nz1;
+  if (p.dd_sep) {
+    p.kd0 = nz1 + 1;
+    p.kd1 = -1;
+    for (int k = 0; k <= nz1; ++k)
+      if (fv3_level_reads_uava(c->nord_h.data(), k)) {
+        p.kd0 = std::min(p.kd0, k);
+        p.kd1 = std::max(p.kd1, k);
+      }
+  }
+  p.side_store = p.kfz <= nz1 && p.heat_in_march && !p.wind_overlap && !fv3_sw_is(FV3SW_DSW_SIDE, "copy");
+  p.side_from = p.side_store ? p.kfz : 1 << 30;
+  p.side_seg = p.side_store ? sx_march_seg(c, nz1 - p.fdw_k0 + 1) : 0;
+  return p;
+}
+
+// FV3_DEBUG_FD: what the plan chose, on stderr (the scalars' line before their launches, the wind stages' before theirs: the marches report between the two)
+static void dsw_report(const DswPlan &p, int nz, bool wind) {
+  if (!p.debug) return;
+  if (!wind) {
+    if (p.fused_scalars) fprintf(stderr, "[d_sw] fd_k0 = %d of %d\n", p.fd_k0, nz);
+    return;
+  }
+  fprintf(stderr, "[d_sw] sponge levels' wind chain: levels 0..%d (fdw_k0 %d) %s\n", p.ks1, p.fdw_k0, p.sponge_forked ? "on the auxiliary stream" : "in program order");
+  fprintf(stderr, "[d_sw] fused wind stage on levels %d..%d of %d\n", p.kfz, nz - 1, nz);
+  if (p.kfz <= nz - 1) fprintf(stderr, "[d_sw] side copies by the wind stage: %s (segment %d)\n", p.side_store ? "yes" : "no", p.side_seg);
+}
+
 // Does d_sw take the accumulators' first-sub-step form (fv3_seq_hints::acc_first) in this configuration?  (the fused scalar marches and fxadv do; the
 // round-1 "separate" transports accumulate through tp2d's epilogue and do not) -- fv3_acoustic_step asks before it leaves out the four zero launches.
-bool dsw_honors_acc_first(const fv3_ctx *c) {
-  int nmax = 0;
-  for (int k = 0; k < c->g.nz; ++k) nmax = std::max(nmax, std::max(c->nord_v_h[k], std::max(c->nord_w_h[k], c->nord_t_h[k])));
-  return !fv3_sw_is(FV3SW_DSW_SCALARS, "separate") && nmax <= 2 && c->zeros;
-}
+bool dsw_honors_acc_first(const fv3_ctx *c) { return dsw_plan(c, false, nullptr).fused_scalars && c->zeros; }
+// Can d_sw leave cx / cy alone and keep the sub-step's Courant numbers in arrays of their own (fv3_seq_hints::acc_defer)?  fxadv stores them exactly where it
+// accumulates them; the round-1 ("separate") scalar form does not go through it with the sequencer's flags.
+bool dsw_can_defer_acc(const fv3_ctx *c) { return dsw_honors_acc_first(c); }
 
 // Deferred accumulation of the Courant numbers (fv3_ctx::acc_slots): crx / cry of the n sub-steps of a call, each in its own array, summed ONCE into cx / cy on
 // their write sets -- ((0 + s1) + s2) + ..., the association the read-modify-write of every sub-step has (0 + s1: what the first sub-step's store computes on the
@@ -935,294 +1077,209 @@ static int acc_sum(fv3_ctx *c, Real *cx, Real *cy, int n, void *stream) {
   return fv3_post(c, (fv3_stream_t)stream, "acc_sum");
 }
 
-// Can d_sw leave cx / cy alone and keep the sub-step's Courant numbers in arrays of their own (fv3_seq_hints::acc_defer)?  fxadv stores them exactly where it
-// accumulates them; the round-1 ("separate") scalar form does not go through it with the sequencer's flags.
-bool dsw_can_defer_acc(const fv3_ctx *c) { return dsw_honors_acc_first(c); }
+// The operator's fields (checked by fv3_d_sw_out).  o_*: where the new delp / pt / w / q_con go (== the inputs: in place).
+struct DswFields {
+  Real *delpc, *delp, *pt, *u, *v, *w, *uc, *vc, *ua, *va, *divgd, *mfx, *mfy, *cx, *cy, *crx, *cry, *xfx, *yfx, *q_con, *heat_source;
+  Real *o_delp, *o_pt, *o_w, *o_q_con;
+  Real dt;
+};
 
-// o_*: where the new delp / pt / w / q_con go.  Null: in place (the operator's own contract: the marches write beside the old
-// fields, which their neighbours still read, and a copy-back follows); fv3_acoustic_step hands in the other half of its
-// ping-pong pair instead and the copy-back disappears.
-int fv3_d_sw_out(fv3_ctx *c, const fv3_field *delpc_, const fv3_field *delp_, const fv3_field *pt_, const fv3_field *u_, const fv3_field *v_,
-                 const fv3_field *w_, const fv3_field *uc_, const fv3_field *vc_, const fv3_field *ua_, const fv3_field *va_,
-                 const fv3_field *divgd_, const fv3_field *mfx_, const fv3_field *mfy_, const fv3_field *cx_, const fv3_field *cy_,
-                 const fv3_field *crx_, const fv3_field *cry_, const fv3_field *xfx_, const fv3_field *yfx_, const fv3_field *q_con_,
-                 const fv3_field *zh_, const fv3_field *heat_source_, const fv3_field *diss_est_, double dtd, void *stream,
-                 const fv3_field *o_delp_, const fv3_field *o_pt_, const fv3_field *o_w_, const fv3_field *o_q_con_, int (*after_scalars)(void *), void *after_user) {
-  if (!c) return FV3_ERR_ARG;
-  FV3_FIELD(delpc, delpc_) FV3_FIELD(delp, delp_) FV3_FIELD(pt, pt_) FV3_FIELD(u, u_) FV3_FIELD(v, v_) FV3_FIELD(w, w_) FV3_FIELD(uc, uc_)
-  FV3_FIELD(vc, vc_) FV3_FIELD(ua, ua_) FV3_FIELD(va, va_) FV3_FIELD(divgd, divgd_) FV3_FIELD(mfx, mfx_) FV3_FIELD(mfy, mfy_) FV3_FIELD(cx, cx_)
-  FV3_FIELD(cy, cy_) FV3_FIELD(crx, crx_) FV3_FIELD(cry, cry_) FV3_FIELD(xfx, xfx_) FV3_FIELD(yfx, yfx_) FV3_FIELD(q_con, q_con_)
-  FV3_FIELD(heat_source, heat_source_)
-  (void)zh_;
-  (void)diss_est_;  // accumulated only with do_skeb (unsupported); kept for signature parity
-  const bool oop = o_delp_ != nullptr;  // out of place
-  Real *o_delp = delp, *o_pt = pt, *o_w = w, *o_q_con = q_con;
-  if (oop) {
-    if (!o_pt_ || !o_w_ || !o_q_con_) return fv3_fail(c, FV3_ERR_ARG, "d_sw: the four output fields come together");
-    o_delp = fv3_chk(c, o_delp_, "o_delp");
-    o_pt = fv3_chk(c, o_pt_, "o_pt");
-    o_w = fv3_chk(c, o_w_, "o_w");
-    o_q_con = fv3_chk(c, o_q_con_, "o_q_con");
-    if (!o_delp || !o_pt || !o_w || !o_q_con) return FV3_ERR_ARG;
-    if (o_delp == delp || o_pt == pt || o_w == w || o_q_con == q_con) return fv3_fail(c, FV3_ERR_ARG, "d_sw: an output field aliases its input");
-  }
+// d_sw's scratch map: the ONLY place of the operator's path that indexes c->scratch (the callees in other files -- tp2d, del6_vt_flux*, dsw_scalars_stream,
+// wind_stage_march -- take pointers).  Streams: M = the caller's, A = the auxiliary one (M itself without one: everything below is then in program order).
+// Levels: nz1 = nz - 1; fd_k0 / fdw_k0 / kfz / ks1 = kfz - 1 as in DswPlan.  "Cannot meet" = why two uses of one slot never overlap in time on the same levels.
+//
+//   slot            name(s)        stage: use, stream, levels                                                      cannot meet because
+//   SC_A, SC_B      ut, vt         fxadv writes (M, all); corner KE of the staged (M / A, 0..ks1) and fused (M,     read-only after fxadv; with wind_overlap the reader
+//                                  kfz..nz1) wind stages reads                                                      on A waits for EV_FXADV_DONE
+//   SC_C, SC_D      dQ_x, dQ_y     fused scalars: q_con's damping fluxes, written A, read by the marches M (all)    EV_CHAIN_DP orders writer and reader;
+//                   fx, fy         separate scalars: air-mass fluxes; vorticity stage: tp2d's flux arrays (M / A)   the vorticity stage follows the scalars on M (its
+//                                                                                                                   low levels on A fork from M after them)
+//   SC_E, SC_F      gx, gy         scalars: air-mass / tracer fluxes of the marches (M, all)                        the wind stages write them only with keep_uv_dx,
+//                   (ut2, vt2)     staged wind, keep_uv_dx only: pre-update v*dy / u*dx (M, 0..nz1)                 which excludes wind_overlap: program order on M;
+//                   utd, vtd       vorticity stage: wk's damping fluxes / increments (A 0..fdw_k0-1, M fdw_k0..nz1) the two streams of the vorticity stage own
+//                                  -> damping heat (M, after EV_SUB_JOIN)                                           disjoint levels
+//   SC_G, SC_U      dC_x, dC_y     scalars: w's damping fluxes, written A, read M                                   EV_CHAIN_DP (fused) / EV_CHAIN_W (separate)
+//   SC_H            heat_s         scalars write (M); damping heat / vorticity march reads (M)                      program order on M
+//   SC_I            ke             staged wind (M / A, 0..ks1), fused wind (M, kfz..nz1); vorticity stage reads     disjoint levels; the march on M waits for
+//                                  (A 0..fdw_k0-1, M fdw_k0..nz1)                                                   EV_STAGED_READY before it reads levels fdw_k0..ks1
+//   SC_J            wk             as ke
+//   SC_L            dnew           divergence iteration's result: staged (M / A, 0..ks1), fused (M, kfz..nz1)       disjoint levels
+//   SC_M            dd_tmp         work array of divdamp_stream (M / A, 0..ks1) and divdamp_patches (M, kfz..nz1)   disjoint levels
+//   SC_N .. SC_Q    n_dp, n_w,     scalars, in place: the new fields until the copy-back (M; A for the sponge       inside the scalars stage (dsw_scalars_stream joins);
+//                   n_qc, n_pt     levels of dsw_scalars_stream) / separate form: the flux-form updates
+//   SC_N, SC_O      u_pre, v_pre   fused wind: side copies on kfz..nz1 (M, side_store: never with wind_overlap);    after the scalars on M; the side copies live on
+//                                  vorticity stage: winds before the damping (A 0..fdw_k0-1, M the rest) -> heat    levels whose u_pre / v_pre the march does not store
+//   SC_R            vabs           staged wind writes 0..fdw_k0-1 (M / A); vorticity transport reads them (A / M)   same stream, or M joined into A (EV_SUB_FORK)
+//   SC_S, SC_T      dB_x, dB_y     scalars: pt's damping fluxes, written A, read M                                  EV_CHAIN_DP (fused) / EV_CHAIN_PT, EV_PAIR_B_FREE
+//   SC_DN_FX, _FY   dA_x, dA_y     scalars: delp's damping fluxes (separate form: then q_con's), written A, read M  EV_CHAIN_DP, EV_PAIR_A_FREE, EV_CHAIN_QC
+//   SC_DN_D2        d2w            scalars: del-n work array of the four chains (A, one after the other)            the chains precede the wind stages on A
+//                   vdamp          wind stages: corner damping field (staged M / A 0..ks1, fused M kfz..nz1)        (wind_overlap) or are joined into M before them
+//                                  -> vorticity march / damping heat read (M)                                       (EV_CHAIN_DP ...); staged / fused: disjoint levels
+//   SC_TP_FY2, _FX2 wuc, wvc       fused wind: the chain's windows of uc / vc (M, kfz..nz1); tp2d's inner fluxes    disjoint levels
+//                                  in the vorticity transport of the low levels (A, 0..fdw_k0-1)
+//   SC_TP_QI        d2v            vorticity stage: del-n work array of wk (A 0..fdw_k0-1, M fdw_k0..nz1)           disjoint levels
+//
+// The forked sponge chain (DswPlan::sponge_forked) shares SC_I, SC_J, SC_L, SC_M, SC_DN_D2, SC_TP_FX2 / FY2, SC_TP_QI and uc / vc (the iteration's work values) with
+// the fused wind stage and the vorticity march: every kernel of the chain touches levels 0..ks1 only, every kernel beside it levels kfz..nz1 only (the vorticity
+// march: fdw_k0..nz1, after EV_STAGED_READY).  Bitwise tests cannot check this (a race can pass by luck): a new use of one of these slots has to keep to its levels.
+struct DswScratch {
+  Real *ut, *vt, *fx, *fy, *dQ_x, *dQ_y, *gx, *gy, *utd, *vtd, *dC_x, *dC_y, *heat_s, *ke, *wk, *dnew, *dd_tmp, *n_dp, *n_w, *n_qc, *n_pt, *u_pre, *v_pre, *vabs;
+  Real *dB_x, *dB_y, *dA_x, *dA_y, *d2w, *vdamp, *wuc, *wvc, *d2v;
+};
+static DswScratch dsw_scratch(const fv3_ctx *c) {
+  DswScratch q;
+  q.ut = c->scratch[SC_A], q.vt = c->scratch[SC_B];
+  q.fx = q.dQ_x = c->scratch[SC_C], q.fy = q.dQ_y = c->scratch[SC_D];
+  q.gx = q.utd = c->scratch[SC_E], q.gy = q.vtd = c->scratch[SC_F];
+  q.dC_x = c->scratch[SC_G], q.dC_y = c->scratch[SC_U];
+  q.heat_s = c->scratch[SC_H], q.ke = c->scratch[SC_I], q.wk = c->scratch[SC_J], q.dnew = c->scratch[SC_L], q.dd_tmp = c->scratch[SC_M];
+  q.n_dp = q.u_pre = c->scratch[SC_N], q.n_w = q.v_pre = c->scratch[SC_O], q.n_qc = c->scratch[SC_P], q.n_pt = c->scratch[SC_Q];
+  q.vabs = c->scratch[SC_R], q.dB_x = c->scratch[SC_S], q.dB_y = c->scratch[SC_T];
+  q.dA_x = c->scratch[SC_DN_FX], q.dA_y = c->scratch[SC_DN_FY], q.d2w = q.vdamp = c->scratch[SC_DN_D2];
+  q.wuc = c->scratch[SC_TP_FY2], q.wvc = c->scratch[SC_TP_FX2], q.d2v = c->scratch[SC_TP_QI];
+  return q;
+}
+
+// the del-n controls of the scalars' chains: delp and pt (vt), w, q_con (t)
+struct DswDeln {
+  Deln vt, w, t;
+};
+static DswDeln dsw_deln(const fv3_ctx *c, const DswPlan &p) {
+  const Geo &g = c->g;
+  return {Deln{g.nord_v, c->tab.tp_vt, g.damp_vt, 0, (Real)0, false, (Real)1.0e-4, p.nord_max_v}, Deln{g.nord_w, c->tab.d6_w, g.damp_w, 0, (Real)0, false, (Real)1.0e-5, p.nord_max_w},
+          Deln{g.nord_t, c->tab.tp_t, g.damp_t, 0, (Real)0, false, (Real)1.0e-4, p.nord_max_t}};
+}
+
+// ---- scalars, fused form.  Air mass, vertical velocity, condensate, potential temperature: the four del-n chains (bandwidth-bound, the fields themselves are
+//      their only input) first, fxadv beside them, then ONE march for the four transports, the divisions by the new air mass and w's damping increment / heat
+//      (fv3_tp4.hip).  The march reads the old fields through its halo columns / rows while it produces the new ones, so it writes beside them.
+static void dsw_scalars_fused(fv3_ctx *c, const DswPlan &p, const DswFields &f, const DswScratch &sc) {
   const Geo g = c->g;
-  fv3_stream_t s = (fv3_stream_t)stream;
-  const Real dt = (Real)dtd;
+  const fv3_stream_t s = p.s, s2 = p.s_aux;
+  const int nz1 = g.nz - 1, fd_k0 = p.fd_k0;
+  const DswDeln dn = dsw_deln(c, p);
+  Real *delp = f.delp, *pt = f.pt, *w = f.w, *q_con = f.q_con, *d2w = sc.d2w;
+  Real *n_dp = p.oop ? f.o_delp : sc.n_dp, *n_w = p.oop ? f.o_w : sc.n_w, *n_qc = p.oop ? f.o_q_con : sc.n_qc, *n_pt = p.oop ? f.o_pt : sc.n_pt;
+  dsw_report(p, g.nz, false);
+  fv3_signal(c, s, EV_FORK);
+  fxadv(c, s, f.uc, f.vc, f.crx, f.cry, f.xfx, f.yfx, sc.ut, sc.vt, f.dt, p.acc_defer ? nullptr : f.cx, p.acc_defer ? nullptr : f.cy, true);
+  fv3_signal(c, s, EV_FXADV_DONE);  // (what the wind stages on the auxiliary stream wait for: DswPlan::wind_overlap)
+  fv3_wait(c, s2, EV_FORK);
+  // (the patches first: they are all the marches of the levels from fd_k0 on wait for; the chains of the sponge layers are read by
+  //  the sponge-layer marches, which follow them on the auxiliary stream)
+  del6_vt_flux_patches(c, s2, delp, d2w, sc.dA_x, sc.dA_y, dn.vt, false, fd_k0, nz1);
+  del6_vt_flux_patches(c, s2, w, d2w, sc.dC_x, sc.dC_y, dn.w, false, fd_k0, nz1);
+  del6_vt_flux_patches(c, s2, q_con, d2w, sc.dQ_x, sc.dQ_y, dn.t, true, fd_k0, nz1);
+  del6_vt_flux_patches(c, s2, pt, d2w, sc.dB_x, sc.dB_y, dn.vt, true, fd_k0, nz1);
+  if (p.split_levels) fv3_signal(c, s2, EV_CHAIN_DP);
+  del6_vt_flux(c, s2, delp, d2w, sc.dA_x, sc.dA_y, dn.vt, false, 0, fd_k0 - 1);
+  del6_vt_flux(c, s2, w, d2w, sc.dC_x, sc.dC_y, dn.w, false, 0, fd_k0 - 1);
+  del6_vt_flux(c, s2, q_con, d2w, sc.dQ_x, sc.dQ_y, dn.t, true, 0, fd_k0 - 1);
+  del6_vt_flux(c, s2, pt, d2w, sc.dB_x, sc.dB_y, dn.vt, true, 0, fd_k0 - 1);
+  if (!p.split_levels) fv3_signal(c, s2, EV_CHAIN_DP);
+  fv3_wait(c, s, EV_CHAIN_DP);
+  DswScalars q4{delp, w, q_con, pt, n_dp, n_w, n_qc, n_pt, sc.heat_s, f.crx, f.cry, f.xfx, f.yfx, f.mfx, f.mfy, sc.gx, sc.gy, sc.dA_x, sc.dA_y, sc.dQ_x, sc.dQ_y, sc.dB_x, sc.dB_y,
+                sc.dC_x, sc.dC_y, c->cfg.hord_dp, c->cfg.hord_vt, c->cfg.hord_tm, dn.vt, dn.t, f.dt, dn.w, fd_k0};
+  q4.acc_first = c->seq.acc_first;
+  q4.zeros = c->zeros;
+  dsw_scalars_stream(c, s, q4, p.scalars_mode);
+  if (!p.oop) launch3<4>(c, s, Box{1, g.nx, 1, g.ny, 0, nz1}, [=] FV3_HD(int t, int k, int i, int j) {
+    const long p = t * g.st + k * g.sk + IX(i, j);
+    delp[p] = n_dp[p];
+    pt[p] = n_pt[p];
+    w[p] = n_w[p];
+    q_con[p] = n_qc[p];
+  });
+}
+
+// ---- scalars, separate form (FV3_DSW_SCALARS=separate, or a del-n order above 2).  The del-n damping chains of delp / w / q_con / pt are bandwidth-bound and need
+//      only the field itself; the transports are issue-bound.  The chains therefore run on the auxiliary stream, one transport ahead (two pairs of flux arrays, A
+//      and B), and overlap with fxadv and the transports on the main stream.
+static void dsw_scalars_separate(fv3_ctx *c, const DswPlan &p, const DswFields &f, const DswScratch &sc) {
+  const Geo g = c->g;
   const fv3_acoustic_config cf = c->cfg;
-  const DampTables tab = c->tab;
+  const fv3_stream_t s = p.s, s2 = p.s_aux;
   const int nz1 = g.nz - 1;
-  const int isd = 1 - g.nh, ied = g.nx + g.nh, jsd = 1 - g.nh, jed = g.ny + g.nh;
-  Real *ut = c->scratch[SC_A], *vt = c->scratch[SC_B], *fx = c->scratch[SC_C], *fy = c->scratch[SC_D], *gx = c->scratch[SC_E], *gy = c->scratch[SC_F];
-  Real *heat_s = c->scratch[SC_H], *ke = c->scratch[SC_I], *wk = c->scratch[SC_J];
-  int nord_max_v = 0, nord_max_w = 0, nord_max_t = 0, nord_max = 0;
-  for (int k = 0; k < g.nz; ++k) {
-    nord_max_v = std::max(nord_max_v, c->nord_v_h[k]);
-    nord_max_w = std::max(nord_max_w, c->nord_w_h[k]);
-    nord_max_t = std::max(nord_max_t, c->nord_t_h[k]);
-    nord_max = std::max(nord_max, c->nord_h[k]);
-  }
+  const DswDeln dn = dsw_deln(c, p);
+  const Real dt = f.dt;
+  Real *delp = f.delp, *pt = f.pt, *w = f.w, *q_con = f.q_con, *crx = f.crx, *cry = f.cry, *xfx = f.xfx, *yfx = f.yfx, *o_delp = f.o_delp, *o_pt = f.o_pt, *o_w = f.o_w, *o_q_con = f.o_q_con;
+  Real *fx = sc.fx, *fy = sc.fy, *gx = sc.gx, *gy = sc.gy, *heat_s = sc.heat_s, *d2w = sc.d2w, *dA_x = sc.dA_x, *dA_y = sc.dA_y, *dB_x = sc.dB_x, *dB_y = sc.dB_y;
+  fv3_signal(c, s, EV_FORK);
+  fv3_wait(c, s2, EV_FORK);
+  del6_vt_flux(c, s2, delp, d2w, dA_x, dA_y, dn.vt, false, 0, nz1);
+  fv3_signal(c, s2, EV_CHAIN_DP);
+  // (w's damping fluxes get their own pair: the kernel that applies them runs after the transports)
+  Real *dC_x = sc.dC_x, *dC_y = sc.dC_y;
+  del6_vt_flux(c, s2, w, d2w, dC_x, dC_y, dn.w, false, 0, nz1);
+  fv3_signal(c, s2, EV_CHAIN_W);
 
-  // The del-n damping chains of delp / w / q_con / pt are bandwidth-bound and need only the field itself;
-  // the transports are issue-bound.  The chains therefore run on the auxiliary stream, one transport
-  // ahead (two pairs of flux arrays, A and B), and overlap with fxadv and the transports on the main stream.
-  //   events: 0 fork | 1..4 chain of delp, w, q_con, pt ready | 5 pair A consumed | 6 pair B consumed
-  fv3_stream_t s2 = fv3_aux(c, s);
-  Real *dA_x = c->scratch[SC_DN_FX], *dA_y = c->scratch[SC_DN_FY], *dB_x = c->scratch[SC_S], *dB_y = c->scratch[SC_T], *d2w = c->scratch[SC_DN_D2];
-  Deln dn_vt{g.nord_v, tab.tp_vt, g.damp_vt, 0, (Real)0, false, (Real)1.0e-4, nord_max_v};
-  Deln dn_w{g.nord_w, tab.d6_w, g.damp_w, 0, (Real)0, false, (Real)1.0e-5, nord_max_w};
-  Deln dn_t{g.nord_t, tab.tp_t, g.damp_t, 0, (Real)0, false, (Real)1.0e-4, nord_max_t};
-  // FV3_DSW_SCALARS=separate: the four transports as four launches + the division kernel (round-1 form, A/B reference)
-  const int sc_env = fv3_sw(FV3SW_DSW_SCALARS);  // (0 default, 1 separate, 2 quad; read per call: the A/B parity test flips it in one process)
-  const bool fused_scalars = sc_env != 1 && nord_max_v <= 2 && nord_max_t <= 2 && nord_max_w <= 2;
-  if (c->seq.acc_first && !fused_scalars) return fv3_fail(c, FV3_ERR_ARG, "d_sw: the sequencer's first-sub-step form of the accumulators needs the fused scalar marches");
-  const int scalars_mode = sc_env == 2 ? 0 : 1;
-  // deferred accumulation of the Courant numbers (fv3_step.hip): cx / cy are not touched by fxadv; crx / cry are this sub-step's own arrays (the sequencer hands them in)
-  const bool acc_defer = c->seq.acc_defer;
-  if (acc_defer && !fused_scalars) return fv3_fail(c, FV3_ERR_ARG, "d_sw: the sequencer's deferred accumulation needs the fused scalar marches (fxadv with the Courant numbers)");
-  if (fused_scalars) {
-    // ---- air mass, vertical velocity, condensate, potential temperature: the four del-n chains (bandwidth-bound, the
-    //      fields themselves are their only input) first, fxadv beside them, then ONE march for the four transports, the
-    //      divisions by the new air mass and w's damping increment / heat (fv3_tp4.hip).  The march reads the old
-    //      fields through its halo columns / rows while it produces the new ones, so it writes beside them.
-    Real *dQ_x = c->scratch[SC_C], *dQ_y = c->scratch[SC_D], *dC_x = c->scratch[SC_G], *dC_y = c->scratch[SC_U];
-    Real *n_dp = oop ? o_delp : c->scratch[SC_N], *n_w = oop ? o_w : c->scratch[SC_O], *n_qc = oop ? o_q_con : c->scratch[SC_P], *n_pt = oop ? o_pt : c->scratch[SC_Q];
-    // Levels from fd_k0 on (every chain switched on and of order 2: all but the sponge layers) run the chains INSIDE the marches
-    // (fv3_tp4.hip, FD); only the faces on the cube-corner patches are computed here for them.  FV3_DSW_DELN=arrays: the
-    // chains of every level as del6_stream launches (round-2 form, A/B reference).
-    int fd_k0 = g.nz;
-    if (!fv3_sw_is(FV3SW_DSW_DELN, "arrays") && scalars_mode == 1) {  // (read per call: the A/B parity test flips it in one process)
-      for (int k = g.nz - 1; k >= 0; --k) {
-        const bool all2 = c->nord_v_h[k] == 2 && c->nord_w_h[k] == 2 && c->nord_t_h[k] == 2 && c->damp_vt_h[k] > 1.0e-4 && c->damp_w_h[k] > 1.0e-5 && c->damp_t_h[k] > 1.0e-4;
-        if (!all2) break;
-        fd_k0 = k;
-      }
-    }
-    if (fv3_sw(FV3SW_DEBUG_FD)) fprintf(stderr, "[d_sw] fd_k0 = %d of %d\n", fd_k0, g.nz);
-    fv3_signal(c, s, 0);
-    fxadv(c, s, uc, vc, crx, cry, xfx, yfx, ut, vt, dt, acc_defer ? nullptr : cx, acc_defer ? nullptr : cy, true);
-    fv3_signal(c, s, 5);  // (fxadv done: what the wind branch on the auxiliary stream waits for, see below)
-    fv3_wait(c, s2, 0);
-    // (the patches first: they are all the marches of the levels from fd_k0 on wait for; the chains of the sponge layers are read by
-    //  the sponge-layer marches, which follow them on the auxiliary stream)
-    del6_vt_flux_patches(c, s2, delp, d2w, dA_x, dA_y, dn_vt, false, fd_k0, nz1);
-    del6_vt_flux_patches(c, s2, w, d2w, dC_x, dC_y, dn_w, false, fd_k0, nz1);
-    del6_vt_flux_patches(c, s2, q_con, d2w, dQ_x, dQ_y, dn_t, true, fd_k0, nz1);
-    del6_vt_flux_patches(c, s2, pt, d2w, dB_x, dB_y, dn_vt, true, fd_k0, nz1);
-    const bool split_levels = s2 != s && scalars_mode == 1 && fd_k0 > 0 && fd_k0 <= nz1;  // (dsw_scalars_stream puts the sponge layers on s2)
-    if (split_levels) fv3_signal(c, s2, 1);
-    del6_vt_flux(c, s2, delp, d2w, dA_x, dA_y, dn_vt, false, 0, fd_k0 - 1);
-    del6_vt_flux(c, s2, w, d2w, dC_x, dC_y, dn_w, false, 0, fd_k0 - 1);
-    del6_vt_flux(c, s2, q_con, d2w, dQ_x, dQ_y, dn_t, true, 0, fd_k0 - 1);
-    del6_vt_flux(c, s2, pt, d2w, dB_x, dB_y, dn_vt, true, 0, fd_k0 - 1);
-    if (!split_levels) fv3_signal(c, s2, 1);
-    fv3_wait(c, s, 1);
-    DswScalars q4{delp, w, q_con, pt, n_dp, n_w, n_qc, n_pt, heat_s, crx, cry, xfx, yfx, mfx, mfy, gx, gy, dA_x, dA_y, dQ_x, dQ_y, dB_x, dB_y, dC_x, dC_y,
-                  cf.hord_dp, cf.hord_vt, cf.hord_tm, dn_vt, dn_t, dt, dn_w, fd_k0};
-    q4.acc_first = c->seq.acc_first;
-    q4.zeros = c->zeros;
-    dsw_scalars_stream(c, s, q4, scalars_mode);
-    if (!oop) launch3<4>(c, s, Box{1, g.nx, 1, g.ny, 0, nz1}, [=] FV3_HD(int t, int k, int i, int j) {
-      const long p = t * g.st + k * g.sk + IX(i, j);
-      delp[p] = n_dp[p];
-      pt[p] = n_pt[p];
-      w[p] = n_w[p];
-      q_con[p] = n_qc[p];
-    });
-  } else {
-  fv3_signal(c, s, 0);
-    fv3_wait(c, s2, 0);
-    del6_vt_flux(c, s2, delp, d2w, dA_x, dA_y, dn_vt, false, 0, nz1);
-    fv3_signal(c, s2, 1);
-    // (w's damping fluxes get their own pair: the kernel that applies them runs after the transports)
-    Real *dC_x = c->scratch[SC_G], *dC_y = c->scratch[SC_U];
-    del6_vt_flux(c, s2, w, d2w, dC_x, dC_y, dn_w, false, 0, nz1);
-    fv3_signal(c, s2, 2);
+  fxadv(c, s, f.uc, f.vc, crx, cry, xfx, yfx, sc.ut, sc.vt, dt, f.cx, f.cy, true);
 
-    fxadv(c, s, uc, vc, crx, cry, xfx, yfx, ut, vt, dt, cx, cy, true);
-
-    // ---- air mass.  The flux-form updates (delp + div, delp * q + div) are formed inside the transport
-    //      kernel (TpEpi); the tracer fluxes gx / gy never reach memory.
-    Real *dpn = c->scratch[SC_N], *w_dp = c->scratch[SC_O], *qc_dp = c->scratch[SC_P], *pt_dp = c->scratch[SC_Q];
-    {
-      // cx += crx, cy += cry happen in fxadv; mfx += fx, mfy += fy in the store stage of this transport
-      const TpEpi e{dpn, nullptr, true, mfx, mfy, nullptr, nullptr, nullptr, false, nullptr, nullptr, nullptr, dA_x, dA_y, nullptr, nullptr, nullptr, nullptr, nullptr};
-      fv3_wait(c, s, 1);
-      tp2d(c, s, delp, crx, cry, xfx, yfx, fx, fy, nullptr, nullptr, nullptr, cf.hord_dp, &dn_vt, 0, nz1, &e);
-      fv3_signal(c, s, 5);
-    }
-    fv3_wait(c, s2, 5);
-    del6_vt_flux(c, s2, q_con, d2w, dA_x, dA_y, dn_t, true, 0, nz1);
-    fv3_signal(c, s2, 3);
-
-    // ---- vertical velocity: transport with the mass fluxes; its del-n damping increment dw and the heat it
-    //      dissipates are formed by the post-transport kernel below straight from the damping fluxes (the old w is
-    //      still in place there), so neither a dw field nor a separate pass over the fluxes exists
-    fv3_wait(c, s, 2);
-    fv3_signal(c, s, 6);
-    fv3_wait(c, s2, 6);
-    del6_vt_flux(c, s2, pt, d2w, dB_x, dB_y, dn_vt, true, 0, nz1);
-    fv3_signal(c, s2, 4);
-    {
-      const TpEpi e{w_dp, delp, false, nullptr, nullptr, nullptr, nullptr, nullptr, false, nullptr, nullptr, nullptr, nullptr, nullptr};  // delp * w + div
-      tp2d(c, s, w, crx, cry, xfx, yfx, gx, gy, fx, fy, nullptr, cf.hord_vt, nullptr, 0, nz1, &e);
-    }
-    // ---- condensate
-    {
-      const TpEpi e{qc_dp, delp, false, nullptr, nullptr, nullptr, nullptr, nullptr, false, nullptr, nullptr, nullptr, dA_x, dA_y};
-      fv3_wait(c, s, 3);
-      tp2d(c, s, q_con, crx, cry, xfx, yfx, gx, gy, fx, fy, delp, cf.hord_dp, &dn_t, 0, nz1, &e);
-    }
-    // ---- potential temperature, then the divisions by the new air mass
-    {
-      const TpEpi e{pt_dp, delp, false, nullptr, nullptr, nullptr, nullptr, nullptr, false, nullptr, nullptr, nullptr, dB_x, dB_y};
-      fv3_wait(c, s, 4);  // (also the join: nothing is left on the auxiliary stream after this chain)
-      tp2d(c, s, pt, crx, cry, xfx, yfx, gx, gy, fx, fy, delp, cf.hord_tm, &dn_vt, 0, nz1, &e);
-    }
-    launch3(c, s, Box{1, g.nx, 1, g.ny, 0, nz1}, [=] FV3_HD(int t, int k, int i, int j) {
-      const long b = t * g.st + k * g.sk;
-      const unsigned q = IX(i, j);
-      const long p = b + q;
-      const Real dpnv = dpn[p];
-      o_delp[p] = dpnv;
-      o_pt[p] = pt_dp[p] / dpnv;
-      Real wn = w_dp[p] / dpnv, hs = (Real)0;
-      if (g.damp_w[k] > (Real)1.0e-5) {
-        const Real dd8 = g.ke_bg[k] * fabs(dt);
-        const Real dwv = ((dC_x + b)[q] - (dC_x + b)[IX(i + 1, j)] + (dC_y + b)[q] - (dC_y + b)[IX(i, j + 1)]) * g.rarea[t * g.st2 + q];
-        hs = dd8 - dwv * (w[p] + (Real)0.5 * dwv);  // (w[p]: still the pre-transport value)
-        wn = wn + dwv;
-      }
-      o_w[p] = wn;
-      heat_s[p] = hs;
-      o_q_con[p] = qc_dp[p] / dpnv;
-    });
-  }
-
-  // ---- The wind branch up to the divergence-damping coefficient: cell-mean vorticity, corner kinetic energy, divergence damping, corner
-  //      interpolation of the vorticity.  It needs fxadv's contravariant winds and the D-grid winds, NOT the scalar transports -- and its
-  //      kernels are bandwidth-bound thread-per-point / light marching kernels, while the scalar marches next to them are bound by
-  //      instruction issue at two waves per SIMD.  Round 4: with an auxiliary stream it is queued THERE, behind the sponge-layer launches,
-  //      and can run beside the scalar marches of the main stream (FV3_DSW_WIND_OVERLAP=1; default: in program order behind them, the round-3
-  //      sequence; same values).  Arrays: it writes wk / vabs / ke / the damping field (scratch the marches do not touch: the del-n work
-  //      array is free once the corner patches are done, and the sponge-layer chains that still use it precede the branch on the same
-  //      stream), delpc, divgd and the dead C-grid winds; the flux slots SC_E / SC_F it would share with the air-mass fluxes are only used
-  //      in the keep_uv_dx configuration, which keeps the program order.
-  Real *vabs = c->scratch[SC_R];
-  Real *vdamp = c->scratch[SC_DN_D2];  // damping field "vort" on corners
-  int fdw_k0 = g.nz;
-  bool keep_uv_dx = false;
-  const bool heat_separate = fv3_sw_is(FV3SW_DSW_HEAT, "separate");
-  bool heat_in_march = false;  // the vorticity march forms the damping heat (set with fdw_k0 below)
-  const fv3_stream_t s_main = s;
-  bool sponge_forked = false;  // the sponge levels' wind chain runs on the auxiliary stream (forked at the top of wind_branch, joined after the vorticity march)
-  int side_from = 1 << 30;  // first level whose damping-heat side copies the fused wind stage has stored (see WindStage::u_side)
-  auto wind_branch = [&](fv3_stream_t s) {
-  // ---- cell-mean relative vorticity (+ absolute vorticity)
-  // Levels that form the damping heat (d_con > 1e-5) WITHOUT vorticity damping (damp_vt <= 1e-5) read the
-  // pre-update u*dx / v*dy where the damping fluxes would be (the work arrays keep those values in the
-  // reference's data flow); only non-default configs (do_vort_damp off / vtdm4 = 0) have such levels.
-  for (int k = 0; k < g.nz; ++k) keep_uv_dx = keep_uv_dx || (c->d_con_h[k] > 1.0e-5 && !(c->damp_vt_h[k] > 1.0e-5));
-  Real *ut2 = c->scratch[SC_E], *vt2 = c->scratch[SC_F];  // = the utd / vtd slots below (damping fluxes overwrite them on damped levels)
-  // Levels from fdw_k0 on (vorticity damping of order 2: all but the sponge layers): the vorticity transport loads wk and adds f0
-  // itself and runs wk's del-n chain inside its march (tp2d TF_WIND | TF_FD) -- no absolute-vorticity field, no del6_stream launch
-  // over those levels but for the tile-edge strips.  FV3_DSW_VORT_DELN=arrays: the round-2 form (A/B reference).
+  // ---- air mass.  The flux-form updates (delp + div, delp * q + div) are formed inside the transport
+  //      kernel (TpEpi); the tracer fluxes gx / gy never reach memory.
+  Real *dpn = sc.n_dp, *w_dp = sc.n_w, *qc_dp = sc.n_qc, *pt_dp = sc.n_pt;
   {
-    const bool off = fv3_sw_is(FV3SW_DSW_VORT_DELN, "arrays") || fv3_sw_is(FV3SW_TP2D_MODE, "staged") || fv3_sw_is(FV3SW_DEL6_MODE, "staged") || keep_uv_dx;
-    if (!off)
-      for (int k = g.nz - 1; k >= 0; --k) {
-        if (!(c->nord_v_h[k] == 2 && c->damp_vt_h[k] > 1.0e-5)) break;
-        fdw_k0 = k;
-      }
+    // cx += crx, cy += cry happen in fxadv; mfx += fx, mfy += fy in the store stage of this transport
+    const TpEpi e{dpn, nullptr, true, f.mfx, f.mfy, nullptr, nullptr, nullptr, false, nullptr, nullptr, nullptr, dA_x, dA_y, nullptr, nullptr, nullptr, nullptr, nullptr};
+    fv3_wait(c, s, EV_CHAIN_DP);
+    tp2d(c, s, delp, crx, cry, xfx, yfx, fx, fy, nullptr, nullptr, nullptr, cf.hord_dp, &dn.vt, 0, nz1, &e);
+    fv3_signal(c, s, EV_PAIR_A_FREE);
   }
-  heat_in_march = cf.d_con > 1.0e-5 && !heat_separate && fdw_k0 <= nz1 && tp2d_fd_lean(c, cf.hord_vt, fdw_k0, nz1);
-  // Round 5, FV3_DSW_VORT_IN_KE=1 (experiment R5-30, off by default): the corner-KE march, which reads u and v anyway, forms the vorticity of the cells under
-  // its corners -- columns 4 .. nx - 2, rows 3 .. ny - 3 at least -- and this launch only serves the four windows of the frame around them (sub-domains
-  // without a tile edge on a side get those cells from both: the same values).  Same bits; measured neutral: the launch goes from 1.61 to 0.25 ms, the march
-  // from 3.00 to 4.15 (23 more registers at four waves per SIMD, three more metric rows, one more store stream).
-  const bool vort_in_ke = fv3_sw(FV3SW_DSW_VORT_IN_KE) && !keep_uv_dx && !fv3_sw(FV3SW_KE_STAGED) && g.nx >= 12 && g.ny >= 12;
-  // Round 6: levels from kfz on run the FUSED wind stage (fv3_wind.hip: vorticity, corner KE, damping chain, corner interpolation and the damping in one
-  // march); the launches below then only serve the levels under kfz (the sponge layers: no chain, absolute-vorticity field).  FV3_DSW_WINDSTAGE=staged:
-  // every level through the staged kernels (A/B; read per call: the parity test flips it).
-  int kfz = g.nz;
+  fv3_wait(c, s2, EV_PAIR_A_FREE);
+  del6_vt_flux(c, s2, q_con, d2w, dA_x, dA_y, dn.t, true, 0, nz1);
+  fv3_signal(c, s2, EV_CHAIN_QC);
+
+  // ---- vertical velocity: transport with the mass fluxes; its del-n damping increment dw and the heat it
+  //      dissipates are formed by the post-transport kernel below straight from the damping fluxes (the old w is
+  //      still in place there), so neither a dw field nor a separate pass over the fluxes exists
+  fv3_wait(c, s, EV_CHAIN_W);
+  fv3_signal(c, s, EV_PAIR_B_FREE);
+  fv3_wait(c, s2, EV_PAIR_B_FREE);
+  del6_vt_flux(c, s2, pt, d2w, dB_x, dB_y, dn.vt, true, 0, nz1);
+  fv3_signal(c, s2, EV_CHAIN_PT);
   {
-    static const bool ke_staged_env = fv3_sw(FV3SW_KE_STAGED), dd_staged_env = fv3_sw(FV3SW_DIVDAMP_STAGED);
-    const bool off = fv3_sw_is(FV3SW_DSW_WINDSTAGE, "staged") || ke_staged_env || dd_staged_env || keep_uv_dx || vort_in_ke || nord_max > DD_NMAX || nord_max <= 0 || g.nx < 8 || g.ny < 8;
-    if (!off)
-      for (int k = g.nz - 1; k >= fdw_k0; --k) {
-        if (!(c->nord_h[k] >= 1 && c->nord_h[k] <= DD_NMAX)) break;
-        kfz = k;
-      }
+    const TpEpi e{w_dp, delp, false, nullptr, nullptr, nullptr, nullptr, nullptr, false, nullptr, nullptr, nullptr, nullptr, nullptr};  // delp * w + div
+    tp2d(c, s, w, crx, cry, xfx, yfx, gx, gy, fx, fy, nullptr, cf.hord_vt, nullptr, 0, nz1, &e);
   }
-  const int ks1 = kfz - 1;  // last level of the staged kernels
-  // Round 6: with the fused stage on every other level, the staged kernels only serve the sponge layers (3 of 79 levels: launches of a few dozen waves, 0.05 -
-  // 0.3 ms each, ~0.8 ms in a row with the gaps between them).  Their whole chain -- vorticity, corner KE, divergence + damping, corner interpolation, the
-  // vorticity's del-n fluxes, the vorticity transport with the wind update -- touches no level the march works on, so it goes to the auxiliary stream and runs
-  // BESIDE the fused stage and the vorticity march (events 2 = fork here, 4 = the staged fields are there: levels from fdw_k0 on feed the vorticity march,
-  // 3 = join after the march).  FV3_DSW_SPONGE_WIND=serial: program order (A/B; per call).
-  fv3_stream_t ss = s;
+  // ---- condensate
   {
-    if (kfz <= nz1 && ks1 >= 0 && fdw_k0 <= kfz && s == s_main && !fv3_sw_is(FV3SW_DSW_SPONGE_WIND, "serial")) ss = fv3_aux(c, s);
-    if (ss != s) {
-      fv3_signal(c, s, 2);
-      fv3_wait(c, ss, 2);
-      sponge_forked = true;
+    const TpEpi e{qc_dp, delp, false, nullptr, nullptr, nullptr, nullptr, nullptr, false, nullptr, nullptr, nullptr, dA_x, dA_y};
+    fv3_wait(c, s, EV_CHAIN_QC);
+    tp2d(c, s, q_con, crx, cry, xfx, yfx, gx, gy, fx, fy, delp, cf.hord_dp, &dn.t, 0, nz1, &e);
+  }
+  // ---- potential temperature, then the divisions by the new air mass
+  {
+    const TpEpi e{pt_dp, delp, false, nullptr, nullptr, nullptr, nullptr, nullptr, false, nullptr, nullptr, nullptr, dB_x, dB_y};
+    fv3_wait(c, s, EV_CHAIN_PT);  // (also the join: nothing is left on the auxiliary stream after this chain)
+    tp2d(c, s, pt, crx, cry, xfx, yfx, gx, gy, fx, fy, delp, cf.hord_tm, &dn.vt, 0, nz1, &e);
+  }
+  launch3(c, s, Box{1, g.nx, 1, g.ny, 0, nz1}, [=] FV3_HD(int t, int k, int i, int j) {
+    const long b = t * g.st + k * g.sk;
+    const unsigned q = IX(i, j);
+    const long p = b + q;
+    const Real dpnv = dpn[p];
+    o_delp[p] = dpnv;
+    o_pt[p] = pt_dp[p] / dpnv;
+    Real wn = w_dp[p] / dpnv, hs = (Real)0;
+    if (g.damp_w[k] > (Real)1.0e-5) {
+      const Real dd8 = g.ke_bg[k] * fabs(dt);
+      const Real dwv = ((dC_x + b)[q] - (dC_x + b)[IX(i + 1, j)] + (dC_y + b)[q] - (dC_y + b)[IX(i, j + 1)]) * g.rarea[t * g.st2 + q];
+      hs = dd8 - dwv * (w[p] + (Real)0.5 * dwv);  // (w[p]: still the pre-transport value)
+      wn = wn + dwv;
     }
-    if (fv3_sw(FV3SW_DEBUG_FD)) fprintf(stderr, "[d_sw] sponge levels' wind chain: levels 0..%d (fdw_k0 %d) %s\n", ks1, fdw_k0, ss != s ? "on the auxiliary stream" : "in program order");
-  }
-  if (fv3_sw(FV3SW_DEBUG_FD)) fprintf(stderr, "[d_sw] fused wind stage on levels %d..%d of %d\n", kfz, nz1, g.nz);
-  // (two levels per thread: the six metric terms are read once)
-  auto vort_cells = [=] FV3_HD(int t, int kp, int i, int j) {
-    const long m2 = t * g.st2;
-    const unsigned p = IX(i, j), pn = IX(i, j + 1), pe_ = IX(i + 1, j);
-    const Real dx0 = (g.dx + m2)[p], dx1 = (g.dx + m2)[pn], dy0 = (g.dy + m2)[p], dy1 = (g.dy + m2)[pe_], ra = (g.rarea + m2)[p], f0v = (g.f0 + m2)[p];
-#pragma unroll 1
-    for (int kk = 0; kk < FV3_KC; ++kk) {
-      const int k = FV3_KC * kp + kk;
-      if (k > ks1) break;
-      const long b = t * g.st + k * g.sk;
-      // wk = rarea * (u*dx - (u*dx)[j+1] - v*dy + (v*dy)[i+1])
-      const Real a = (u + b)[p] * dx0, a1 = (u + b)[pn] * dx1;
-      const Real e = (v + b)[p] * dy0, e1 = (v + b)[pe_] * dy1;
-      const Real wkv = ra * (a - a1 - e + e1);
-      (wk + b)[p] = wkv;
-      if (k < fdw_k0) (vabs + b)[p] = wkv + f0v;  // absolute vorticity for the transport below (formed on load from fdw_k0 on)
-      if (keep_uv_dx) {
-        (vt2 + b)[p] = a;
-        (ut2 + b)[p] = e;
-      }
-    }
-  };
-  {
-    const int nkc = (ks1 + FV3_KC) / FV3_KC;
-    if (nkc <= 0) {
-    } else if (vort_in_ke)
-      launch_frame(c, ss, Frame{{Box{isd, 3, jsd, jed, 0, nkc - 1}, Box{g.nx - 1, ied, jsd, jed, 0, 0}, Box{4, g.nx - 2, jsd, 2, 0, 0}, Box{4, g.nx - 2, g.ny - 2, jed, 0, 0}}}, vort_cells);
-    else
-      launch3(c, ss, Box{isd, ied, jsd, jed, 0, nkc - 1}, vort_cells);
-  }
-  // ---- kinetic energy on corners (vb * ytp_v + ub * xtp_u)
-  static const bool ke_staged = fv3_sw(FV3SW_KE_STAGED);  // A/B switch for profiling
+    o_w[p] = wn;
+    heat_s[p] = hs;
+    o_q_con[p] = qc_dp[p] / dpnv;
+  });
+}
+
+// ---- kinetic energy on corners (vb * ytp_v + ub * xtp_u), one thread per corner, levels k0 .. k1: on the frame -- the 3 outermost corner rows / columns next to a
+//      cube-tile edge, which the marches (ke_stream, wind_stage_march) leave out -- or, every_corner (FV3_KE_STAGED), on all of them
+static void dsw_ke_points(fv3_ctx *c, fv3_stream_t s, const DswFields &f, const DswScratch &sc, int k0, int k1, bool every_corner) {
+  const Geo g = c->g;
+  const fv3_acoustic_config cf = c->cfg;
+  const Real dt = f.dt;
+  Real *u = f.u, *v = f.v, *uc = f.uc, *vc = f.vc, *ut = sc.ut, *vt = sc.vt, *ke = sc.ke;
   // ke_value: one corner, any position (tile-edge forms of ub / vb, one-sided PPM, corner overrides)
   auto ke_value = [=] FV3_HD(int t, int k, int i, int j) -> Real {
     const int fl = g.flags[t];
@@ -1285,40 +1342,78 @@ int fv3_d_sw_out(fv3_ctx *c, const fv3_field *delpc_, const fv3_field *delp_, co
     return kev;
   };
   auto ke_point = [=] FV3_HD(int t, int k, int i, int j) { (ke + t * g.st + k * g.sk)[IX(i, j)] = ke_value(t, k, i, j); };
+  if (every_corner) {
+    launch3(c, s, Box{1, g.nx + 1, 1, g.ny + 1, k0, k1}, ke_point);
+    return;
+  }
+  // (W / E: columns 1..3 / npx-2..npx as narrow windows, S / N: rows 1..3 / npy-2..npy; the corner cells belong to the column windows)
+  launch_frame_w(c, s, Frame{{Box{1, 3, 1, g.ny + 1, k0, k1}, Box{g.npx - 2, g.npx, 1, g.ny + 1, 0, 0}, Box{1, g.nx + 1, 1, 3, 0, 0}, Box{1, g.nx + 1, g.npy - 2, g.npy, 0, 0}}},
+                 [=] FV3_HD(int w_, int t, int k, int i, int j) {
+    const int fl = g.flags[t];
+    if (!(fl & (w_ == 0 ? FV3_W : w_ == 1 ? FV3_E : w_ == 2 ? FV3_S : FV3_N))) return;
+    if (w_ >= 2 && (((fl & FV3_W) && i <= 3) || ((fl & FV3_E) && i >= g.npx - 2))) return;  // covered by the column windows
+    ke_point(t, k, i, j);
+  });
+}
+
+// ---- wind stages, levels 0 .. ks1 through the staged kernels (stream p.s_sponge; the in-place iteration of the staged divergence damping on p.s_wind): cell-mean
+//      relative vorticity (+ absolute vorticity), corner kinetic energy, divergence and its damping, the iteration, the corner interpolation of the vorticity with
+//      the damping as its epilogue.  They need fxadv's contravariant winds and the D-grid winds, NOT the scalar transports.  Arrays: they write wk / vabs / ke / the
+//      damping field, delpc, divgd and the dead C-grid winds (see the table at DswScratch).
+static void dsw_wind_staged(fv3_ctx *c, const DswPlan &p, const DswFields &f, const DswScratch &sc) {
+  const Geo g = c->g;
+  const fv3_acoustic_config cf = c->cfg;
+  const DampTables tab = c->tab;
+  const fv3_stream_t s = p.s_wind, ss = p.s_sponge;
+  const Real dt = f.dt;
+  const int nz1 = g.nz - 1, ks1 = p.ks1, fdw_k0 = p.fdw_k0, kd0 = p.kd0, kd1 = p.kd1, nord_max = p.nord_max;
+  const int isd = 1 - g.nh, ied = g.nx + g.nh, jsd = 1 - g.nh, jed = g.ny + g.nh;
+  const bool keep_uv_dx = p.keep_uv_dx, vort_in_ke = p.vort_in_ke, dd_sep = p.dd_sep, keep_divgd = p.keep_divgd;
+  Real *u = f.u, *v = f.v, *uc = f.uc, *vc = f.vc, *ua = f.ua, *va = f.va, *delpc = f.delpc, *divgd = f.divgd;
+  Real *wk = sc.wk, *vabs = sc.vabs, *ke = sc.ke, *vdamp = sc.vdamp;  // vdamp: damping field "vort" on corners
+  Real *ut2 = sc.utd, *vt2 = sc.vtd;  // (keep_uv_dx: the damping fluxes overwrite them on damped levels)
+  // (two levels per thread: the six metric terms are read once)
+  auto vort_cells = [=] FV3_HD(int t, int kp, int i, int j) {
+    const long m2 = t * g.st2;
+    const unsigned p = IX(i, j), pn = IX(i, j + 1), pe_ = IX(i + 1, j);
+    const Real dx0 = (g.dx + m2)[p], dx1 = (g.dx + m2)[pn], dy0 = (g.dy + m2)[p], dy1 = (g.dy + m2)[pe_], ra = (g.rarea + m2)[p], f0v = (g.f0 + m2)[p];
+#pragma unroll 1
+    for (int kk = 0; kk < FV3_KC; ++kk) {
+      const int k = FV3_KC * kp + kk;
+      if (k > ks1) break;
+      const long b = t * g.st + k * g.sk;
+      // wk = rarea * (u*dx - (u*dx)[j+1] - v*dy + (v*dy)[i+1])
+      const Real a = (u + b)[p] * dx0, a1 = (u + b)[pn] * dx1;
+      const Real e = (v + b)[p] * dy0, e1 = (v + b)[pe_] * dy1;
+      const Real wkv = ra * (a - a1 - e + e1);
+      (wk + b)[p] = wkv;
+      if (k < fdw_k0) (vabs + b)[p] = wkv + f0v;  // absolute vorticity for the transport below (formed on load from fdw_k0 on)
+      if (keep_uv_dx) {
+        (vt2 + b)[p] = a;
+        (ut2 + b)[p] = e;
+      }
+    }
+  };
+  {
+    const int nkc = (ks1 + FV3_KC) / FV3_KC;
+    if (nkc <= 0) {
+    } else if (vort_in_ke)
+      launch_frame(c, ss, Frame{{Box{isd, 3, jsd, jed, 0, nkc - 1}, Box{g.nx - 1, ied, jsd, jed, 0, 0}, Box{4, g.nx - 2, jsd, 2, 0, 0}, Box{4, g.nx - 2, g.ny - 2, jed, 0, 0}}}, vort_cells);
+    else
+      launch3(c, ss, Box{isd, ied, jsd, jed, 0, nkc - 1}, vort_cells);
+  }
   if (ks1 < 0) {
-  } else if (ke_staged) {
-    launch3(c, ss, Box{1, g.nx + 1, 1, g.ny + 1, 0, ks1}, ke_point);
+  } else if (p.ke_staged) {
+    dsw_ke_points(c, ss, f, sc, 0, ks1, true);
   } else {
     ke_stream(c, ss, u, v, uc, vc, ke, dt, cf.hord_mt, 0, ks1, vort_in_ke ? wk : nullptr, vabs, fdw_k0);
-    // frame: the 3 outermost corner rows / columns next to a cube-tile edge
-    // (W / E: columns 1..3 / npx-2..npx as narrow windows, S / N: rows 1..3 / npy-2..npy; the corner cells belong to the column windows)
-    launch_frame_w(c, ss, Frame{{Box{1, 3, 1, g.ny + 1, 0, ks1}, Box{g.npx - 2, g.npx, 1, g.ny + 1, 0, 0}, Box{1, g.nx + 1, 1, 3, 0, 0}, Box{1, g.nx + 1, g.npy - 2, g.npy, 0, 0}}},
-                   [=] FV3_HD(int w_, int t, int k, int i, int j) {
-      const int fl = g.flags[t];
-      if (!(fl & (w_ == 0 ? FV3_W : w_ == 1 ? FV3_E : w_ == 2 ? FV3_S : FV3_N))) return;
-      if (w_ >= 2 && (((fl & FV3_W) && i <= 3) || ((fl & FV3_E) && i >= g.npx - 2))) return;  // covered by the column windows
-      ke_point(t, k, i, j);
-    });
+    dsw_ke_points(c, ss, f, sc, 0, ks1, false);
   }
 
   // ---- divergence damping.  delpc: un-iterated divergence; divgd iterated in place; uc / vc are
   //      the work arrays of the iteration exactly as in the reference (their C-grid values are dead).
-  // nord == 0 levels: divergence of the D-grid wind on the fly; nord > 0 levels: delpc = divgd
-  static const bool staged_dd = fv3_sw(FV3SW_DIVDAMP_STAGED);  // A/B switch for profiling
-  // the marching iteration writes its result beside divgd, so the un-iterated divergence stays readable there and
-  // the nord > 0 levels need no copy of it into delpc
-  const bool dd_sep = !(staged_dd || nord_max > DD_NMAX);
-  // (with the separate result array only the nord == 0 levels -- the sponge layers -- have work here: the launch covers their range)
-  int kd0 = 0, kd1 = nz1;
-  if (dd_sep) {
-    kd0 = nz1 + 1;
-    kd1 = -1;
-    for (int k = 0; k <= nz1; ++k)
-      if (c->nord_h[k] == 0) {
-        kd0 = std::min(kd0, k);
-        kd1 = std::max(kd1, k);
-      }
-  }
+  // Levels that read ua / va (no iteration): divergence of the D-grid wind on the fly; the others: delpc = divgd, unless the iteration writes beside divgd
+  // (DswPlan::dd_sep: then only the levels kd0 .. kd1 have work here and the launch covers their range)
   // (ss: with the fused stage on, dd_sep holds and the levels kd0 .. kd1 -- those without the iteration -- are sponge levels)
   launch3(c, ss, Box{1, g.nx + 1, 1, g.ny + 1, kd0, kd1}, [=] FV3_HD(int t, int k, int i, int j) {
     const int fl = g.flags[t];
@@ -1326,7 +1421,7 @@ int fv3_d_sw_out(fv3_ctx *c, const fv3_field *delpc_, const fv3_field *delp_, co
     const bool W = fl & FV3_W, E = fl & FV3_E, S = fl & FV3_S, N = fl & FV3_N;
     const int npx = g.npx, npy = g.npy;
     const unsigned p = IX(i, j);
-    if (g.nord[k] != 0) {
+    if (!fv3_level_reads_uava(g.nord, k)) {
       if (!dd_sep) (delpc + b)[p] = (divgd + b)[p];
       return;
     }
@@ -1349,181 +1444,162 @@ int fv3_d_sw_out(fv3_ctx *c, const fv3_field *delpc_, const fv3_field *delp_, co
     if (W && N && i == 1 && j == npy) d += VRT(1, npy);
     d = (g.rarea_c + m2)[p] * d;
     (delpc + b)[p] = d;
-    const Real damp = g.da_min_c * fv3_max(g.d2_divg[k], fv3_min((Real)0.20, (Real)cf.dddmp * fabs(d * dt)));
+    const Real damp = fv3_damp_coef(g.da_min_c, g.d2_divg[k], (Real)cf.dddmp, fabs(d * dt));
     const Real vd = damp * d;
     (vdamp + b)[p] = vd;
     (ke + b)[p] += vd;
   });
   // divergence-damping iteration: divgd -> dnew (levels with nord > 0)
-  Real *dnew = divgd;
-  {
-    if (!dd_sep) {
-      divdamp_staged(c, s, divgd, uc, vc, nord_max, 0, nz1, nullptr);
-    } else if (nord_max > 0) {
-      dnew = c->scratch[SC_L];
-      if (ks1 >= 0) divdamp_stream(c, ss, divgd, dnew, uc, vc, c->scratch[SC_M], nord_max, 0, ks1);
-    }
-  }
+  Real *dnew = p.dnew_sep ? sc.dnew : divgd;
+  if (!dd_sep)
+    divdamp_staged(c, s, divgd, uc, vc, nord_max, 0, nz1, nullptr);
+  else if (p.dnew_sep && ks1 >= 0)
+    divdamp_stream(c, ss, divgd, dnew, uc, vc, sc.dd_tmp, nord_max, 0, ks1);
   // Smagorinsky-type coefficient from the corner-interpolated vorticity, levels with nord > 0
   // (wkb, the corner vorticity, is no longer a field: see the a2b epilogue below)
   // Corner vorticity (a2b_ord4 of wk) is consumed once, pointwise, by the Smagorinsky-type damping below: that
   // kernel runs as the epilogue of the corner interpolation and the corner field is never stored.
-  {
-    const Real dddmp = (Real)cf.dddmp;
-    // The operator's contract leaves the iterated divergence in divgd (D_SW-Out carries it).  Inside fv3_acoustic_step nobody reads it: the
-    // next c_sw overwrites the workspace field -- the sequencer says so (seq.divgd_dead) and the copy of the iteration's result into divgd
-    // (one field write per call) is skipped when the iteration wrote beside it.
-    const bool keep_divgd = !(c->seq.divgd_dead && dd_sep);
-    if (ks1 >= 0) a2b_ord4_t<8>(c, ss, wk, 0, 0, ks1 + 1, (Real)1, [=] FV3_HD(int t, int k, unsigned p, Real wkbv) {
-      const int nord = g.nord[k];
-      if (nord == 0) return;
-      const long b = t * g.st + k * g.sk;
-      const Real dpc = dd_sep ? (divgd + b)[p] : (delpc + b)[p];  // the un-iterated divergence
-      Real vo = (Real)0;
-      if (dddmp >= (Real)1.0e-5) vo = fabs(dt) * sqrt(dpc * dpc + wkbv * wkbv);
-      const Real damp2 = g.da_min_c * fv3_max(g.d2_divg[k], fv3_min((Real)0.20, dddmp * vo));
-      const Real dn_ = (dnew + b)[p];
-      if (keep_divgd) (divgd + b)[p] = dn_;  // (no-op for the in-place staged form; skipped inside the sequencer: see seq.divgd_dead)
-      const Real vd = damp2 * dpc + tab.dd8[k] * dn_;
-      (vdamp + b)[p] = vd;
-      (ke + b)[p] += vd;
-    });
-    if (ss != s) fv3_signal(c, ss, 4);  // (ke, the damping field and wk of the staged levels are final)
-    // ---- the fused wind stage on the levels kfz .. nz1 (fv3_wind.hip).  Order: the damping chain's cube-corner patches first (the march reads their values
-    //      where its own chain is wrong; their work arrays are scratch here -- the march still reads the C-grid winds), the march, then two per-point launches on
-    //      the three outermost corner rows / columns next to a cube-tile edge: kinetic energy (ke_point), then corner vorticity (a2b_point on the wk the march has
-    //      stored) and the damping, with the iterated divergence the march exported there.
-    if (kfz <= nz1) {
-      Real *const wuc = c->scratch[SC_TP_FY2], *const wvc = c->scratch[SC_TP_FX2];
-      dd_copy_windows(c, s, uc, vc, wuc, wvc, kfz, nz1, 2);
-      divdamp_patches(c, s, divgd, dnew, wuc, wvc, c->scratch[SC_M], nord_max, kfz, nz1);
-      WindStage ws{u, v, uc, vc, divgd, ke, vdamp, wk, dnew, tab.dd8, dt, dddmp, cf.hord_mt, keep_divgd, kfz, nz1};
-      // The vorticity march's damping-heat epilogue wants copies of the winds on its segment / strip boundaries, made before it updates them in place: this
-      // march has every row of u and v in registers, so it stores them (sx_side_copy then only serves the levels under kfz).  Not beside the scalar marches:
-      // the arrays hold their new fields then.  FV3_DSW_SIDE=copy: the separate copies (A/B; read per call).
-      if (heat_in_march && s == s_main && !fv3_sw_is(FV3SW_DSW_SIDE, "copy")) {
-        ws.u_side = c->scratch[SC_N];
-        ws.v_side = c->scratch[SC_O];
-        ws.side_seg = sx_march_seg(c, nz1 - fdw_k0 + 1);
-        side_from = kfz;
-      }
-      if (fv3_sw(FV3SW_DEBUG_FD)) fprintf(stderr, "[d_sw] side copies by the wind stage: %s (segment %d)\n", ws.u_side ? "yes" : "no", ws.side_seg);
-      wind_stage_march(c, s, ws);
-      // (two launches: with ke_value and a2b_point in one closure the geometry block went to scratch memory -- 1600 B per lane, 7 ms for these 3 % of the corners)
-      launch_frame_w(c, s, Frame{{Box{1, 3, 1, g.ny + 1, kfz, nz1}, Box{g.npx - 2, g.npx, 1, g.ny + 1, 0, 0}, Box{1, g.nx + 1, 1, 3, 0, 0}, Box{1, g.nx + 1, g.npy - 2, g.npy, 0, 0}}},
-                     [=] FV3_HD(int w_, int t, int k, int i, int j) {
-        const int fl = g.flags[t];
-        if (!(fl & (w_ == 0 ? FV3_W : w_ == 1 ? FV3_E : w_ == 2 ? FV3_S : FV3_N))) return;
-        if (w_ >= 2 && (((fl & FV3_W) && i <= 3) || ((fl & FV3_E) && i >= g.npx - 2))) return;  // covered by the column windows
-        ke_point(t, k, i, j);
-      });
-      const int nfr = g.nx + 1 > g.ny + 1 ? g.nx + 1 : g.ny + 1;
-      launch3(c, s, Box{1, nfr, 1, 12, kfz, nz1}, [=] FV3_HD(int t, int k, int a_, int side) {
-        const int fl = g.flags[t];
-        int i, j;
-        // side 1..3: columns 1..3 (W)   4..6: columns npx-2..npx (E)   7..9: rows 1..3 (S)   10..12: rows npy-2..npy (N)
-        if (side <= 6) {
-          if (a_ > g.ny + 1) return;
-          if (!(fl & (side <= 3 ? FV3_W : FV3_E))) return;
-          i = side <= 3 ? side : g.npx - 6 + side;
-          j = a_;
-        } else {
-          if (a_ > g.nx + 1) return;
-          if (!(fl & (side <= 9 ? FV3_S : FV3_N))) return;
-          j = side <= 9 ? side - 6 : g.npy - 12 + side;
-          i = a_;
-          if (((fl & FV3_W) && i <= 3) || ((fl & FV3_E) && i >= g.npx - 2)) return;  // covered by the column sides
-        }
-        const long b = t * g.st + k * g.sk;
-        const unsigned p = IX(i, j);
-        const Real wkbv = a2b_point(g, wk + b, t, i, j);
-        const Real dpc = (divgd + b)[p];
-        Real vo = (Real)0;
-        if (dddmp >= (Real)1.0e-5) vo = fabs(dt) * sqrt(dpc * dpc + wkbv * wkbv);
-        const Real damp2 = g.da_min_c * fv3_max(g.d2_divg[k], fv3_min((Real)0.20, dddmp * vo));
-        const Real vd = damp2 * dpc + tab.dd8[k] * (dnew + b)[p];
-        (vdamp + b)[p] = vd;
-        (ke + b)[p] += vd;
-      });
-      dd_copy_windows(c, s, wuc, wvc, uc, vc, kfz, nz1, 0);  // (the chain's work values, where the staged form leaves them)
-      // (the operator's own contract leaves the iterated divergence in divgd; inside the sequencer nobody reads it)
-      if (keep_divgd) launch3(c, s, Box{1, g.nx + 1, 1, g.ny + 1, kfz, nz1}, [=] FV3_HD(int t, int k, int i, int j) {
-        const long pp = t * g.st + k * g.sk + IX(i, j);
-        divgd[pp] = dnew[pp];
-      });
+  const Real dddmp = (Real)cf.dddmp;
+  if (ks1 >= 0) a2b_ord4_t<8>(c, ss, wk, 0, 0, ks1 + 1, (Real)1, [=] FV3_HD(int t, int k, unsigned p, Real wkbv) {
+    const int nord = g.nord[k];
+    if (nord == 0) return;
+    const long b = t * g.st + k * g.sk;
+    const Real dpc = dd_sep ? (divgd + b)[p] : (delpc + b)[p];  // the un-iterated divergence
+    Real vo = (Real)0;
+    if (dddmp >= (Real)1.0e-5) vo = fabs(dt) * sqrt(dpc * dpc + wkbv * wkbv);
+    const Real damp2 = fv3_damp_coef(g.da_min_c, g.d2_divg[k], dddmp, vo);
+    const Real dn_ = (dnew + b)[p];
+    if (keep_divgd) (divgd + b)[p] = dn_;  // (no-op for the in-place staged form; skipped inside the sequencer: see seq.divgd_dead)
+    const Real vd = damp2 * dpc + tab.dd8[k] * dn_;
+    (vdamp + b)[p] = vd;
+    (ke + b)[p] += vd;
+  });
+}
+
+// ---- wind stages, levels kfz .. nz1 through the fused stage (fv3_wind.hip), stream p.s_wind.  Order: the damping chain's cube-corner patches first (the march reads
+//      their values where its own chain is wrong; their work arrays are scratch here -- the march still reads the C-grid winds), the march, then two per-point
+//      launches on the three outermost corner rows / columns next to a cube-tile edge: kinetic energy (dsw_ke_points), then corner vorticity (a2b_point on the wk
+//      the march has stored) and the damping, with the iterated divergence the march exported there.
+static void dsw_wind_fused(fv3_ctx *c, const DswPlan &p, const DswFields &f, const DswScratch &sc) {
+  const Geo g = c->g;
+  const DampTables tab = c->tab;
+  const fv3_stream_t s = p.s_wind;
+  const Real dt = f.dt, dddmp = (Real)c->cfg.dddmp;
+  const int nz1 = g.nz - 1, kfz = p.kfz, nord_max = p.nord_max;
+  if (kfz > nz1) return;
+  Real *u = f.u, *v = f.v, *uc = f.uc, *vc = f.vc, *divgd = f.divgd, *wk = sc.wk, *ke = sc.ke, *vdamp = sc.vdamp, *wuc = sc.wuc, *wvc = sc.wvc;
+  Real *dnew = p.dnew_sep ? sc.dnew : divgd;
+  dd_copy_windows(c, s, uc, vc, wuc, wvc, kfz, nz1, 2);
+  divdamp_patches(c, s, divgd, dnew, wuc, wvc, sc.dd_tmp, nord_max, kfz, nz1);
+  WindStage ws{u, v, uc, vc, divgd, ke, vdamp, wk, dnew, tab.dd8, dt, dddmp, c->cfg.hord_mt, p.keep_divgd, kfz, nz1};
+  if (p.side_store) {
+    ws.u_side = sc.u_pre;  // (side copies: on levels whose pre-damping winds the vorticity march does not store)
+    ws.v_side = sc.v_pre;
+    ws.side_seg = p.side_seg;
+  }
+  wind_stage_march(c, s, ws);
+  // (two launches: with ke_value and a2b_point in one closure the geometry block went to scratch memory -- 1600 B per lane, 7 ms for these 3 % of the corners)
+  dsw_ke_points(c, s, f, sc, kfz, nz1, false);
+  const int nfr = g.nx + 1 > g.ny + 1 ? g.nx + 1 : g.ny + 1;
+  launch3(c, s, Box{1, nfr, 1, 12, kfz, nz1}, [=] FV3_HD(int t, int k, int a_, int side) {
+    const int fl = g.flags[t];
+    int i, j;
+    // side 1..3: columns 1..3 (W)   4..6: columns npx-2..npx (E)   7..9: rows 1..3 (S)   10..12: rows npy-2..npy (N)
+    if (side <= 6) {
+      if (a_ > g.ny + 1) return;
+      if (!(fl & (side <= 3 ? FV3_W : FV3_E))) return;
+      i = side <= 3 ? side : g.npx - 6 + side;
+      j = a_;
+    } else {
+      if (a_ > g.nx + 1) return;
+      if (!(fl & (side <= 9 ? FV3_S : FV3_N))) return;
+      j = side <= 9 ? side - 6 : g.npy - 12 + side;
+      i = a_;
+      if (((fl & FV3_W) && i <= 3) || ((fl & FV3_E) && i >= g.npx - 2)) return;  // covered by the column sides
     }
-  }
+    const long b = t * g.st + k * g.sk;
+    const unsigned p = IX(i, j);
+    const Real wkbv = a2b_point(g, wk + b, t, i, j);
+    const Real dpc = (divgd + b)[p];
+    Real vo = (Real)0;
+    if (dddmp >= (Real)1.0e-5) vo = fabs(dt) * sqrt(dpc * dpc + wkbv * wkbv);
+    const Real damp2 = fv3_damp_coef(g.da_min_c, g.d2_divg[k], dddmp, vo);
+    const Real vd = damp2 * dpc + tab.dd8[k] * (dnew + b)[p];
+    (vdamp + b)[p] = vd;
+    (ke + b)[p] += vd;
+  });
+  dd_copy_windows(c, s, wuc, wvc, uc, vc, kfz, nz1, 0);  // (the chain's work values, where the staged form leaves them)
+  // (the operator's own contract leaves the iterated divergence in divgd; inside the sequencer nobody reads it)
+  if (p.keep_divgd) launch3(c, s, Box{1, g.nx + 1, 1, g.ny + 1, kfz, nz1}, [=] FV3_HD(int t, int k, int i, int j) {
+    const long pp = t * g.st + k * g.sk + IX(i, j);
+    divgd[pp] = dnew[pp];
+  });
+}
 
-  };
-  // Measured (same box, alternating runs, C768): d_sw 51.6 -> 50.8 ms, but the halo copies that run inside d_sw 1.96 -> 2.5 and the sub-step
-  // 113.6 -> 114.0 ms: the branch takes from the marches what it gains -- one d_sw call moves 252 GB in 51 ms = 4.9 TB/s, i.e. the operator
-  // as a whole is at the bandwidth the chip sustains; overlapping its parts creates no capacity.  Off by default (FV3_DSW_WIND_OVERLAP=1).
-  static const bool wind_overlap_off = !fv3_sw(FV3SW_DSW_WIND_OVERLAP);
-  for (int k = 0; k < g.nz; ++k) keep_uv_dx = keep_uv_dx || (c->d_con_h[k] > 1.0e-5 && !(c->damp_vt_h[k] > 1.0e-5));
-  const bool wind_overlap = fused_scalars && s2 != s && !wind_overlap_off && !keep_uv_dx;
-  if (wind_overlap) {
-    fv3_wait(c, s2, 5);
-    wind_branch(s2);
-    fv3_signal(c, s2, 6);
+// the wind stages up to the divergence-damping coefficient, on p.s_wind: the staged levels (forked onto the auxiliary stream with DswPlan::sponge_forked), then
+// the fused stage
+static void dsw_wind(fv3_ctx *c, const DswPlan &p, const DswFields &f, const DswScratch &sc) {
+  dsw_report(p, c->g.nz, true);
+  if (p.sponge_forked) {
+    fv3_signal(c, p.s_wind, EV_SUB_FORK);
+    fv3_wait(c, p.s_sponge, EV_SUB_FORK);
   }
+  dsw_wind_staged(c, p, f, sc);
+  if (p.sponge_forked) fv3_signal(c, p.s_sponge, EV_STAGED_READY);  // (ke, the damping field and wk of the staged levels are final)
+  dsw_wind_fused(c, p, f, sc);
+}
 
-  // The new delp / w / q_con / pt are final here; the winds take the second half of the operator.  The sequencer starts the
-  // halo update of delp / pt / q_con at this point (out-of-place form only: nothing below writes them, and the one later read --
-  // the new delp of the damping-heat kernel -- is on compute cells, which a halo update does not touch), so that the exchange
-  // overlaps the whole wind part instead of following the operator.
-  if (after_scalars) {
-    const int hst = after_scalars(after_user);
-    if (hst != FV3_OK) return hst;
-  }
-  if (wind_overlap)
-    fv3_wait(c, s, 6);
-  else
-    wind_branch(s);
-  if (sponge_forked) fv3_wait(c, s, 4);  // (the staged levels from fdw_k0 on feed the march below: level 2 of the 79 -- no divergence-damping chain there, but the vorticity's)
-
-  // ---- del-n damping fluxes of the relative vorticity (they depend on wk alone): ahead of the transport, whose wind
-  //      epilogue applies them
-  Real *utd = c->scratch[SC_E], *vtd = c->scratch[SC_F];  // (the tracer-flux slots: free since the tracer transports are done)
+// ---- vorticity: the del-n damping fluxes of the relative vorticity (they depend on wk alone) ahead of the transport, whose wind epilogue applies them; then the
+//      transport.  Returns the last level the damping-heat kernel still has to serve.
+static int dsw_vorticity(fv3_ctx *c, const DswPlan &p, const DswFields &f, const DswScratch &sc) {
+  const Geo g = c->g;
+  const fv3_acoustic_config cf = c->cfg;
+  const DampTables tab = c->tab;
+  const fv3_stream_t s = p.s;
+  const int nz1 = g.nz - 1, fdw_k0 = p.fdw_k0;
+  Real *u = f.u, *v = f.v, *crx = f.crx, *cry = f.cry, *xfx = f.xfx, *yfx = f.yfx;
+  Real *wk = sc.wk, *ke = sc.ke, *fx = sc.fx, *fy = sc.fy, *utd = sc.utd, *vtd = sc.vtd;  // (utd / vtd: the tracer-flux slots, free since the tracer transports are done)
   {
-    Deln dn_v{g.nord_v, tab.d6_vt, g.damp_vt, 0, (Real)0, false, (Real)1.0e-5, nord_max_v};
-    del6_vt_flux(c, sponge_forked ? fv3_aux(c, s) : s, wk, c->scratch[SC_TP_QI], utd, vtd, dn_v, false, 0, fdw_k0 - 1);
+    Deln dn_v{g.nord_v, tab.d6_vt, g.damp_vt, 0, (Real)0, false, (Real)1.0e-5, p.nord_max_v};
+    del6_vt_flux(c, p.sponge_forked ? p.s_aux : s, wk, sc.d2v, utd, vtd, dn_v, false, 0, fdw_k0 - 1);
     if (tp2d_fd_lean(c, cf.hord_vt, fdw_k0, nz1))  // (the round-5 march runs the chain on every strip: only the cube-corner patches come from the staged chain)
-      del6_vt_flux_patches(c, s, wk, c->scratch[SC_TP_QI], utd, vtd, dn_v, false, fdw_k0, nz1);
+      del6_vt_flux_patches(c, s, wk, sc.d2v, utd, vtd, dn_v, false, fdw_k0, nz1);
     else
-      del6_vt_flux_edge_strips(c, s, wk, c->scratch[SC_TP_QI], utd, vtd, dn_v, false, fdw_k0, nz1);
+      del6_vt_flux_edge_strips(c, s, wk, sc.d2v, utd, vtd, dn_v, false, fdw_k0, nz1);
   }
   // ---- vorticity transport; the wind update u = u*dx + ke - ke[i+1] + fy, v = v*dy + ke - ke[j+1] - fx is the
   //      transport kernel's epilogue (the vorticity fluxes are never stored), and so is the vorticity damping
   //      u += vtd, v -= utd on the levels that have it; the winds BEFORE that damping -- what the damping heat is
   //      formed from -- go to scratch beside
-  Real *u_pre = c->scratch[SC_N], *v_pre = c->scratch[SC_O];
-  int heat_k1 = nz1;  // last level the damping-heat kernel serves
-  {
-    TpEpi e{nullptr, nullptr, false, nullptr, nullptr, u, v, ke, false, nullptr, nullptr, nullptr, nullptr, nullptr, vtd, utd, g.damp_vt, u_pre, v_pre};
-    // (the levels without the chain: a small launch, on the auxiliary stream beside the others -- events 2 = fork, 3 = join)
-    fv3_stream_t sv = fdw_k0 > 0 && fdw_k0 <= nz1 ? fv3_aux(c, s) : s;
-    if (sv != s && !sponge_forked) {  // (forked: the stream already carries the sponge levels' chain, which is all this launch depends on)
-      fv3_signal(c, s, 2);
-      fv3_wait(c, sv, 2);
-    }
-    tp2d(c, sv, vabs, crx, cry, xfx, yfx, fx, fy, nullptr, nullptr, nullptr, cf.hord_vt, nullptr, 0, fdw_k0 - 1, &e);
-    if (sv != s) fv3_signal(c, sv, 3);
-    e.fd = 1;
-    e.fd_coef = tab.d6_vt;
-    e.fd_add = (const Real *)g.f0;
-    // Round 5: on these levels the damping heat is the epilogue of the march (fv3_tp2x.hip, HEAT): the pre-damping winds and the two damping
-    // increments are not stored and the damping-heat kernel below only serves the levels under fdw_k0.  FV3_DSW_HEAT=separate: the round-4
-    // sequence (A/B; read per call).
-    TpHeat th{vdamp, o_delp, heat_s, g.d_con, heat_source, c->seq.heat_first ? c->zeros : nullptr};
-    th.side_from = side_from;
-    if (heat_in_march) e.heat = &th;
-    tp2d(c, s, wk, crx, cry, xfx, yfx, fx, fy, nullptr, nullptr, nullptr, cf.hord_vt, nullptr, fdw_k0, nz1, &e);
-    // (whether the march took the heat over is what the dispatch DID, not what was predicted above: a form that ignores TpEpi::heat leaves every level to the kernel below)
-    if (th.consumed) heat_k1 = fdw_k0 - 1;
-    if (sv != s) fv3_wait(c, s, 3);
+  TpEpi e{nullptr, nullptr, false, nullptr, nullptr, u, v, ke, false, nullptr, nullptr, nullptr, nullptr, nullptr, vtd, utd, g.damp_vt, sc.u_pre, sc.v_pre};
+  // (the levels without the chain: a small launch, on the auxiliary stream beside the others)
+  const fv3_stream_t sv = p.s_vort_low;
+  if (sv != s && !p.sponge_forked) {  // (forked: the stream already carries the sponge levels' chain, which is all this launch depends on)
+    fv3_signal(c, s, EV_SUB_FORK);
+    fv3_wait(c, sv, EV_SUB_FORK);
   }
+  tp2d(c, sv, sc.vabs, crx, cry, xfx, yfx, fx, fy, nullptr, nullptr, nullptr, cf.hord_vt, nullptr, 0, fdw_k0 - 1, &e);
+  if (sv != s) fv3_signal(c, sv, EV_SUB_JOIN);
+  e.fd = 1;
+  e.fd_coef = tab.d6_vt;
+  e.fd_add = (const Real *)g.f0;
+  // Round 5: on these levels the damping heat is the epilogue of the march (fv3_tp2x.hip, HEAT): the pre-damping winds and the two damping
+  // increments are not stored and the damping-heat kernel only serves the levels under fdw_k0.  FV3_DSW_HEAT=separate: the round-4 sequence (A/B).
+  TpHeat th{sc.vdamp, f.o_delp, sc.heat_s, g.d_con, f.heat_source, c->seq.heat_first ? c->zeros : nullptr};
+  th.side_from = p.side_from;
+  if (p.heat_in_march) e.heat = &th;
+  tp2d(c, s, wk, crx, cry, xfx, yfx, fx, fy, nullptr, nullptr, nullptr, cf.hord_vt, nullptr, fdw_k0, nz1, &e);
+  if (sv != s) fv3_wait(c, s, EV_SUB_JOIN);
+  // (whether the march took the heat over is what the dispatch DID, not what the plan predicted: a form that ignores TpEpi::heat leaves every level to the kernel)
+  return th.consumed ? fdw_k0 - 1 : nz1;
+}
 
-  const bool heat_on = cf.d_con > 1.0e-5;
+// ---- damping heat on the levels 0 .. heat_k1 (the others: formed in the vorticity march)
+static void dsw_damping_heat(fv3_ctx *c, const DswPlan &p, const DswFields &f, const DswScratch &sc, int heat_k1) {
+  const Geo g = c->g;
+  const fv3_stream_t s = p.s;
+  Real *heat_source = f.heat_source, *o_delp = f.o_delp, *heat_s = sc.heat_s, *vdamp = sc.vdamp, *utd = sc.utd, *vtd = sc.vtd, *u_pre = sc.u_pre, *v_pre = sc.v_pre;
+  const bool heat_on = c->cfg.d_con > 1.0e-5;
   const bool heat_first = c->seq.heat_first;  // (the sequencer's first sub-step of a call: heat_source holds nothing yet -- 0 + heat, the field is not read)
   // (two levels per thread: the six metric terms are read once)
   if (heat_k1 >= 0) launch3(c, s, Box{1, g.nx, 1, g.ny, 0, (heat_k1 + FV3_KC) / FV3_KC - 1}, [=] FV3_HD(int t, int kp, int i, int j) {
@@ -1554,8 +1630,66 @@ int fv3_d_sw_out(fv3_ctx *c, const fv3_field *delpc_, const fv3_field *delp_, co
       if (heat_on) FV3_ST_NT((heat_source + b)[p], (heat_first ? (Real)0 : (heat_source + b)[p]) + hs);
     }
   });
+}
+
+// o_*: where the new delp / pt / w / q_con go.  Null: in place (the operator's own contract: the marches write beside the old
+// fields, which their neighbours still read, and a copy-back follows); fv3_acoustic_step hands in the other half of its
+// ping-pong pair instead and the copy-back disappears.
+int fv3_d_sw_out(fv3_ctx *c, const fv3_field *delpc_, const fv3_field *delp_, const fv3_field *pt_, const fv3_field *u_, const fv3_field *v_,
+                 const fv3_field *w_, const fv3_field *uc_, const fv3_field *vc_, const fv3_field *ua_, const fv3_field *va_,
+                 const fv3_field *divgd_, const fv3_field *mfx_, const fv3_field *mfy_, const fv3_field *cx_, const fv3_field *cy_,
+                 const fv3_field *crx_, const fv3_field *cry_, const fv3_field *xfx_, const fv3_field *yfx_, const fv3_field *q_con_,
+                 const fv3_field *zh_, const fv3_field *heat_source_, const fv3_field *diss_est_, double dtd, void *stream,
+                 const fv3_field *o_delp_, const fv3_field *o_pt_, const fv3_field *o_w_, const fv3_field *o_q_con_, int (*after_scalars)(void *), void *after_user) {
+  if (!c) return FV3_ERR_ARG;
+  FV3_FIELD(delpc, delpc_) FV3_FIELD(delp, delp_) FV3_FIELD(pt, pt_) FV3_FIELD(u, u_) FV3_FIELD(v, v_) FV3_FIELD(w, w_) FV3_FIELD(uc, uc_)
+  FV3_FIELD(vc, vc_) FV3_FIELD(ua, ua_) FV3_FIELD(va, va_) FV3_FIELD(divgd, divgd_) FV3_FIELD(mfx, mfx_) FV3_FIELD(mfy, mfy_) FV3_FIELD(cx, cx_)
+  FV3_FIELD(cy, cy_) FV3_FIELD(crx, crx_) FV3_FIELD(cry, cry_) FV3_FIELD(xfx, xfx_) FV3_FIELD(yfx, yfx_) FV3_FIELD(q_con, q_con_)
+  FV3_FIELD(heat_source, heat_source_)
+  (void)zh_;
+  (void)diss_est_;  // accumulated only with do_skeb (unsupported); kept for signature parity
+  const bool oop = o_delp_ != nullptr;  // out of place
+  Real *o_delp = delp, *o_pt = pt, *o_w = w, *o_q_con = q_con;
+  if (oop) {
+    if (!o_pt_ || !o_w_ || !o_q_con_) return fv3_fail(c, FV3_ERR_ARG, "d_sw: the four output fields come together");
+    o_delp = fv3_chk(c, o_delp_, "o_delp");
+    o_pt = fv3_chk(c, o_pt_, "o_pt");
+    o_w = fv3_chk(c, o_w_, "o_w");
+    o_q_con = fv3_chk(c, o_q_con_, "o_q_con");
+    if (!o_delp || !o_pt || !o_w || !o_q_con) return FV3_ERR_ARG;
+    if (o_delp == delp || o_pt == pt || o_w == w || o_q_con == q_con) return fv3_fail(c, FV3_ERR_ARG, "d_sw: an output field aliases its input");
+  }
+  const fv3_stream_t s = (fv3_stream_t)stream;
+  const DswFields f{delpc, delp, pt, u, v, w, uc, vc, ua, va, divgd, mfx, mfy, cx, cy, crx, cry, xfx, yfx, q_con, heat_source, o_delp, o_pt, o_w, o_q_con, (Real)dtd};
+  const DswPlan p = dsw_plan(c, oop, s);
+  if (p.fail) return fv3_fail(c, FV3_ERR_ARG, p.fail);
+  const DswScratch sc = dsw_scratch(c);
+  if (p.fused_scalars)
+    dsw_scalars_fused(c, p, f, sc);
+  else
+    dsw_scalars_separate(c, p, f, sc);
+  if (p.wind_overlap) {  // (the wind stages beside the scalar marches, on the auxiliary stream)
+    fv3_wait(c, p.s_aux, EV_FXADV_DONE);
+    dsw_wind(c, p, f, sc);
+    fv3_signal(c, p.s_aux, EV_WIND_DONE);
+  }
+  // The new delp / w / q_con / pt are final here; the winds take the second half of the operator.  The sequencer starts the
+  // halo update of delp / pt / q_con at this point (out-of-place form only: nothing below writes them, and the one later read --
+  // the new delp of the damping-heat kernel -- is on compute cells, which a halo update does not touch), so that the exchange
+  // overlaps the whole wind part instead of following the operator.
+  if (after_scalars) {
+    const int hst = after_scalars(after_user);
+    if (hst != FV3_OK) return hst;
+  }
+  if (p.wind_overlap)
+    fv3_wait(c, s, EV_WIND_DONE);
+  else
+    dsw_wind(c, p, f, sc);
+  // (the staged levels from fdw_k0 on feed the vorticity march: level 2 of the 79 -- no divergence-damping chain there, but the vorticity's)
+  if (p.sponge_forked) fv3_wait(c, s, EV_STAGED_READY);
+  dsw_damping_heat(c, p, f, sc, dsw_vorticity(c, p, f, sc));
   // (deferred accumulation: the last d_sw of an acoustic call forms cx / cy from the sub-steps' Courant numbers)
-  if (acc_defer && c->seq.acc_sum_n > 0) {
+  if (p.acc_defer && c->seq.acc_sum_n > 0) {
     const int st_ = acc_sum(c, cx, cy, c->seq.acc_sum_n, s);
     if (st_ != FV3_OK) return st_;
   }

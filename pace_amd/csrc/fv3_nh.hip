@@ -1419,11 +1419,11 @@ extern "C" int fv3_update_dz_d(fv3_ctx *c, const fv3_field *zs_, const fv3_field
       }
   }
   // (the interfaces without the chain inside the march -- the sponge layers: their del-n launch and their small transport launch go
-  //  to the auxiliary stream, beside the march of the others; events 2 = fork, 3 = join)
+  //  to the auxiliary stream, beside the march of the others; EV_SUB_FORK / EV_SUB_JOIN)
   fv3_stream_t sa = fd_k0 > 0 && fd_k0 <= nz ? fv3_aux(c, s) : s;
   if (sa != s) {
-    fv3_signal(c, s, 2);
-    fv3_wait(c, sa, 2);
+    fv3_signal(c, s, EV_SUB_FORK);
+    fv3_wait(c, sa, EV_SUB_FORK);
   }
   del6_vt_flux(c, sa, zh, d2, fx2, fy2, dn, false, 0, fd_k0 - 1);
   if (tp2d_fd_lean(c, c->cfg.hord_tm, fd_k0, nz))  // (the round-5 march runs the chain on every strip: only the cube-corner patches come from the staged chain)
@@ -1437,11 +1437,11 @@ extern "C" int fv3_update_dz_d(fv3_ctx *c, const fv3_field *zs_, const fv3_field
   {
     TpEpi e{znew, nullptr, false, nullptr, nullptr, nullptr, nullptr, nullptr, true, fx2, fy2, g.damp_vt, nullptr, nullptr};
     tp2d(c, sa, zh, crx_a, cry_a, xfx_a, yfx_a, c->scratch[SC_J], c->scratch[SC_K], nullptr, nullptr, nullptr, c->cfg.hord_tm, nullptr, 0, fd_k0 - 1, &e);
-    if (sa != s) fv3_signal(c, sa, 3);
+    if (sa != s) fv3_signal(c, sa, EV_SUB_JOIN);
     e.fd = 1;
     e.fd_coef = dz_coef;
     tp2d(c, s, zh, crx_a, cry_a, xfx_a, yfx_a, c->scratch[SC_J], c->scratch[SC_K], nullptr, nullptr, nullptr, c->cfg.hord_tm, nullptr, fd_k0, nz, &e);
-    if (sa != s) fv3_wait(c, s, 3);
+    if (sa != s) fv3_wait(c, s, EV_SUB_JOIN);
   }
   if (fv3_sw(FV3SW_DEBUG_FD)) fprintf(stderr, "[update_dz_d] closing scan: %s\n", scan_deferred ? "left to riem_solver3's pre-sweep" : "own kernel");
   if (scan_deferred) {

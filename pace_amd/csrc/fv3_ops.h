@@ -35,6 +35,58 @@ enum {
   SC_COUNT = 28
 };
 
+// Auxiliary-stream events (indices into ctx->aux_events; fv3_signal(c, from, e) records e on `from`, fv3_wait(c, to, e) makes `to` wait for that record).
+// M = the caller's stream, A = the auxiliary one.  An index serves several roles, one after the other: a wait is queued right behind its record (the same host
+// thread, before the next record of that index), and a queued wait keeps the record it saw, so a later record of the same index cannot reach it.
+//
+//   index  name              recorded on / awaited by, in which operator
+//   0      EV_FORK           M / A at an operator's start: d_sw (both scalar forms: the del-n chains of the scalars go to A), c_sw (stage A / B windows go to A)
+//   1      EV_CHAIN_DP       A / M, d_sw: fused scalars -- the damping fluxes of all four scalars are there (split_levels: their cube-corner patches; the sponge levels'
+//                            chains precede the sponge marches on A); separate scalars -- delp's chain
+//          EV_WIN_JOIN       A / M, c_sw: the stage A / B windows are done
+//   2      EV_SUB_FORK       M / A, a small side chain inside an operator: dsw_scalars_stream (sponge levels' marches), update_dz_d (chainless interfaces), d_sw (the
+//                            sponge levels' wind chain; without it the chainless levels of the vorticity transport)
+//          EV_CHAIN_W        A / M, d_sw, separate scalars: w's chain
+//   3      EV_SUB_JOIN       A / M, the join of what EV_SUB_FORK started
+//          EV_CHAIN_QC       A / M, d_sw, separate scalars: q_con's chain
+//   4      EV_STAGED_READY   A / M, d_sw with the sponge levels' wind chain forked: wk / ke / the damping field of the staged levels are final (the vorticity march reads them)
+//          EV_CHAIN_PT       A / M, d_sw, separate scalars: pt's chain (also the join of that form)
+//   5      EV_FXADV_DONE     M / A, d_sw, fused scalars: fxadv is done (awaited only with FV3_DSW_WIND_OVERLAP=1)
+//          EV_PAIR_A_FREE    M / A, d_sw, separate scalars: flux pair A (delp's damping fluxes) is consumed, q_con's chain may overwrite it
+//   6      EV_WIND_DONE      A / M, d_sw with FV3_DSW_WIND_OVERLAP=1: the wind stages on A are done
+//          EV_PAIR_B_FREE    M / A, d_sw, separate scalars: w's chain is joined, pt's chain may start
+//          EV_CSW_LATE_FORK  M / A, c_sw with seq.csw_defer: the stage D / E windows go to A
+//   7      EV_CSW_LATE_JOIN  A / M, the join of those windows: in c_sw itself, or (seq.csw_defer) in fv3_csw_join -- the only event pending across an operator's return
+//
+// Pending at the same time (recorded, its wait not yet queued).  d_sw, fused scalars: EV_FORK with EV_FXADV_DONE; EV_FXADV_DONE stays pending through the scalar
+// marches (EV_CHAIN_DP and dsw_scalars_stream's EV_SUB_FORK / EV_SUB_JOIN come and go meanwhile) until the wind stages take it or the call ends; then EV_SUB_FORK,
+// EV_STAGED_READY and EV_SUB_JOIN of the wind stages, in this order, EV_STAGED_READY across the fused stage's launches.  d_sw, separate scalars: EV_CHAIN_DP with
+// EV_CHAIN_W; EV_CHAIN_W with EV_PAIR_A_FREE, then with EV_CHAIN_QC; EV_CHAIN_QC with EV_CHAIN_PT.  The two scalar forms exclude each other, which is why their
+// names may share indices; the separate form never runs with the sponge fork's EV_STAGED_READY pending (its EV_CHAIN_PT is awaited before the wind stages start).
+// c_sw: EV_FORK .. EV_WIN_JOIN around its march.  With seq.csw_defer EV_CSW_LATE_JOIN stays pending after c_sw returns; fv3_csw_join awaits it before
+// riem_solver_c, i.e. before the d_sw of that sub-step records its own index 5 / 6 events -- and c_sw's wait for index 6 was queued inside c_sw -- so the pair
+// cannot collide with d_sw's.
+enum fv3_event {
+  EV_FORK = 0,
+  EV_CHAIN_DP = 1, EV_WIN_JOIN = 1,
+  EV_SUB_FORK = 2, EV_CHAIN_W = 2,
+  EV_SUB_JOIN = 3, EV_CHAIN_QC = 3,
+  EV_STAGED_READY = 4, EV_CHAIN_PT = 4,
+  EV_FXADV_DONE = 5, EV_PAIR_A_FREE = 5,
+  EV_WIND_DONE = 6, EV_PAIR_B_FREE = 6, EV_CSW_LATE_FORK = 6,
+  EV_CSW_LATE_JOIN = 7
+};
+
+// Does d_sw form the divergence of level k from ua / va?  (nord: the per-level order of the divergence damping -- the host table ctx->nord_h or its device copy
+// Geo::nord; 0 = no damping chain on the level: the divergence of the D-grid wind is formed on the fly from ua / va.)  The ONE statement of a contract between
+// c_sw and d_sw inside the sequencer: between the sub-steps of fv3_acoustic_step c_sw stores ua / va in full only on these levels (elsewhere only its window
+// cells: fv3_seq_hints::uava_thin), and d_sw's divergence kernel and its level range kd0 .. kd1 read them on exactly these levels.
+FV3_HD inline bool fv3_level_reads_uava(const int *nord, int k) { return nord[k] == 0; }
+
+// d_sw's Smagorinsky-type damping coefficient da_min_c * max(d2_bg, min(0.20, dddmp * vo)): vo = |dt| * the corner's |divergence| (levels without the damping chain)
+// or sqrt(divergence^2 + vorticity^2) (the others; 0 with dddmp < 1e-5)
+FV3_HD inline Real fv3_damp_coef(Real da_min_c, Real d2_divg, Real dddmp, Real vo) { return da_min_c * fv3_max(d2_divg, fv3_min((Real)0.20, dddmp * vo)); }
+
 // Per-level del-n control.  Level k uses order nord_k[k] (or nord_u), coefficient damp_k[k]
 // (or damp_u) and is active when on_k[k] > on_thr (or on_u).
 struct Deln {

@@ -250,6 +250,10 @@ struct ProfParentScope {
 //   acc_defer, acc_sum_n     d_sw (acc_sum_n: the last)                       fv3_dsw.hip                    FV3_ACC_DEFER=0
 //   dz_scan                  update_dz_d                                      fv3_nh.hip                     FV3_DZ_SCAN=separate
 //   delz_dead                riem_solver3, all but the last                   fv3_nh.hip                     FV3_SEQ_DELZ=every
+// The contract behind uava_thin, delz_dead and divgd_dead: BETWEEN the sub-steps of one call st->ua / st->va are complete only on the levels where d_sw reads
+// them (fv3_level_reads_uava, fv3_ops.h: the ONE predicate c_sw's store and d_sw's divergence kernel and level range share) and, on the other levels, in the
+// cells c_sw's boundary windows read; delz and the workspace's divgd are stale.  Nothing inside the sequencer reads them there.  All of them are final only
+// after the last sub-step of the call; a call that returns early with an error leaves them in that intermediate state.
 extern "C" int fv3_acoustic_step(fv3_ctx *c, const fv3_state *st, const fv3_workspace *ws, double timestep, int n_map, fv3_halo_fn halo, void *halo_user,
                                  void *stream) {
   if (!c || !st || !ws) return FV3_ERR_ARG;

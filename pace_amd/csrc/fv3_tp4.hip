@@ -928,14 +928,14 @@ void dsw_scalars_stream(fv3_ctx *c, fv3_stream_t s, const DswScalars &a, int mod
     static const bool sponge_serial = fv3_sw(FV3SW_DSW_SPONGE_SERIAL);
     fv3_stream_t s2 = kf > 0 && kf <= nz1 && !sponge_serial ? fv3_aux(c, s) : s;
     if (s2 != s) {
-      fv3_signal(c, s, 2);
-      fv3_wait(c, s2, 2);
+      fv3_signal(c, s, EV_SUB_FORK);
+      fv3_wait(c, s2, EV_SUB_FORK);
     }
     dsw_scalars_t<Q4_AIR, Q4_INTERIOR>(c, s2, a, 0, kf - 1);
     if (edges) dsw_scalars_t<Q4_AIR, Q4_EDGE>(c, s2, a, 0, kf - 1);
     dsw_scalars_t<Q4_TRC, Q4_INTERIOR>(c, s2, a, 0, kf - 1);
     if (edges) dsw_scalars_t<Q4_TRC, Q4_EDGE>(c, s2, a, 0, kf - 1);
-    if (s2 != s) fv3_signal(c, s2, 3);
+    if (s2 != s) fv3_signal(c, s2, EV_SUB_JOIN);
     // (the big launches: the instantiation with the PPM order as a constant when the configuration has the reference's 6 everywhere;
     //  FV3_HORD_CONST=0 keeps the run-time form -- A/B, same values)
     //  Measured: -0.15 ms of d_sw for 12 spilled VGPRs in the two-tracer marches (the branch-free limiter needs ~24 more registers):
@@ -969,7 +969,7 @@ void dsw_scalars_stream(fv3_ctx *c, fv3_stream_t s, const DswScalars &a, int mod
         if (edges) dsw_scalars_t<Q4_TRC, Q4_EDGE, false, true>(c, s, a, kf, nz1);
       }
     }
-    if (s2 != s) fv3_wait(c, s, 3);
+    if (s2 != s) fv3_wait(c, s, EV_SUB_JOIN);
   }
 }
 

@@ -369,7 +369,7 @@ void wind_stage_march_t(fv3_ctx *c, fv3_stream_t s, const WindStage &a) {
           const Real dpc = s_dpc[l];
           Real vo = (Real)0;
           if (dddmp >= (Real)1.0e-5) vo = adt * sqrt(dpc * dpc + wkbv * wkbv);
-          const Real damp2 = da_min_c * fv3_max(d2k, fv3_min((Real)0.20, dddmp * vo));
+          const Real damp2 = fv3_damp_coef(da_min_c, d2k, dddmp, vo);
           const Real vd = damp2 * dpc + dd8 * dn_;
           FV3_ST_NT(*fv3_at(vdb, p), vd);
           *fv3_at(keb, p) = s_kev[l] + vd;
