@@ -114,7 +114,8 @@ typedef struct {
 typedef struct {
   fv3_field u, v, w, ua, va, uc, vc, delp, delz, pt, pe, pk, peln, pkz, q_con, omga, cappa;
   fv3_field mfxd, mfyd, cxd, cyd, diss_estd;
-  fv3_field phis; /* 2-D: shape[2] == 1 */
+  fv3_field phis; /* 2-D: shape[2] == 1.  Read on the compute domain AND one halo ring (riem_solver_c's surface height on the ring of the
+                   * C-grid heights): the caller fills that ring once; no halo update of the call touches phis */
 } fv3_state;
 
 int fv3_version(void);
@@ -133,10 +134,16 @@ int64_t fv3_ctx_scratch_bytes(const fv3_ctx *ctx);
 /* device_sync: true semantics [REF .jenkins/driver_configs/baroclinic_c192_6ranks.yaml:7] */
 int fv3_ctx_set_device_sync(fv3_ctx *ctx, int on);
 
-/* ---- operators (argument order = the reference operator's __call__) ---- */
+/* ---- operators (argument order = the reference operator's __call__) ----
+ * Footprints (held by tests/test_operator_footprints.py; INTEGRATION.md, "Read and write footprints"): an entry reads no pad level (level nz
+ * of a cell-level field), no cube-corner halo block and no halo cell beyond what the reference operator reads; it stores into an argument
+ * only on the region the reference defines that output on, levels 0 .. nz - 1 (interface fields 0 .. nz).  An output defined on the compute
+ * domain + 1 ring (gz, ws, pef, pe, omga, delpc, ptc) is stored on that whole rectangle: the cube-corner halo cell in it, which has no
+ * neighbour, holds no defined value.  The exceptions are stated at the entries below. */
 
 /* CGridShallowWaterDynamics.__call__ [REF tests/savepoint/thresholds/fv_dynamics.yaml:2-75].
- * delpc / ptc are outputs (the reference returns them). */
+ * delpc / ptc are outputs (the reference returns them).  uc, vc, ua, va, ut, vt, divgd, omga, delpc, ptc are not read on entry; uc / vc /
+ * ua / va are stored wherever the reference's d2a2c_vect stores them (halo rows that d_sw and the later stages read included). */
 int fv3_c_sw(fv3_ctx *, const fv3_field *delp, const fv3_field *pt, const fv3_field *u, const fv3_field *v,
              const fv3_field *w, const fv3_field *uc, const fv3_field *vc, const fv3_field *ua,
              const fv3_field *va, const fv3_field *ut, const fv3_field *vt, const fv3_field *divgd,
@@ -158,7 +165,8 @@ int fv3_p_grad_c(fv3_ctx *, const fv3_field *uc, const fv3_field *vc, const fv3_
                  const fv3_field *pkc, const fv3_field *gz, double dt2, void *stream);
 
 /* FiniteVolumeFluxPrep.__call__(uc, vc, crx, cry, xfx, yfx, ut, vt, dt)
- * [REF examples/notebooks/functions.py:877-891] */
+ * [REF examples/notebooks/functions.py:877-891].  ut / vt are stored where the reference stores them: ut on i = 0 .. nx + 3 of every row
+ * (vt: j = 0 .. ny + 3 of every column), on the two rows (columns) along a cube-tile edge only on the faces of crx (cry). */
 int fv3_fxadv(fv3_ctx *, const fv3_field *uc, const fv3_field *vc, const fv3_field *crx, const fv3_field *cry,
               const fv3_field *xfx, const fv3_field *yfx, const fv3_field *ut, const fv3_field *vt, double dt,
               void *stream);
@@ -176,7 +184,9 @@ int fv3_a2b_ord4(fv3_ctx *, const fv3_field *qin, const fv3_field *qout, int kst
                  void *stream);
 
 /* DGridShallowWaterLagrangianDynamics.__call__ [REF tests/savepoint/thresholds/fv_dynamics.yaml:76-170;
- * tests/main/fv3core/test_config.py:14] */
+ * tests/main/fv3core/test_config.py:14].  delpc is the work array of the divergence damping (as the reference's argument of that name): any
+ * cell of it may change, and uc / vc hold work values afterwards.  delpc, crx, cry, xfx, yfx, zh, diss_est are not read
+ * on entry. */
 int fv3_d_sw(fv3_ctx *, const fv3_field *delpc, const fv3_field *delp, const fv3_field *pt, const fv3_field *u,
              const fv3_field *v, const fv3_field *w, const fv3_field *uc, const fv3_field *vc,
              const fv3_field *ua, const fv3_field *va, const fv3_field *divgd, const fv3_field *mfx,

@@ -699,6 +699,8 @@ extern "C" int fv3_c_sw(fv3_ctx *c, const fv3_field *delp_, const fv3_field *pt_
   const int march_env = fv3_sw(FV3SW_CSW_MARCH);  // (0 default, 1 "0", 2 "abc")
   const bool march = b_split && march_env != 1;
   const bool fused = march && march_env != 2;
+  if (fv3_sw(FV3SW_DEBUG_FD))
+    fprintf(stderr, "[c_sw] %s\n", !b_split ? "generic per-point stage kernels everywhere" : fused ? "interior as one march" : march ? "stages A - C as a march" : "two-row stage-B kernel on the interior");
   // levels one thread of the stage kernels walks (the metric terms of its point are read once for them): FV3_KC for launches
   // over whole sub-domains; 2 when they only cover the boundary windows, which are too few points to fill the chip otherwise
   static const int win_kc = fv3_sw(FV3SW_CSW_WIN_KC);

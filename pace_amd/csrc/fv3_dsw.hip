@@ -156,12 +156,14 @@ FV3_HD inline bool fxadv_int_v(const Geo &g, int fl, int i, int j) {
 // cx / cy (optional): accumulated Courant numbers of the tracer sub-cycling, cx += crx, cy += cry on the
 // faces d_sw accumulates them (i in 1..nx+1 resp. j in 1..ny+1, all halo rows / columns)
 // thin_ut: store ut / vt only within 4 cells of a cube-tile edge -- all d_sw reads of them afterwards are the tile-edge
-// forms of the corner kinetic energy (the standalone operator stores them everywhere, as the reference does)
+// forms of the corner kinetic energy (the standalone operator stores them everywhere the reference does: on the tile-edge rows / columns
+// only on the faces of crx / cry -- beside them the reference leaves ut / vt untouched)
 void fxadv(fv3_ctx *c, fv3_stream_t s, const Real *uc, const Real *vc, Real *crx, Real *cry, Real *xfx, Real *yfx, Real *ut, Real *vt, Real dt, Real *cx,
            Real *cy, bool thin_ut) {
   const Geo g = c->g;
   const bool first = c->seq.acc_first;  // (the sequencer's first sub-step of a call: cx / cy hold nothing yet -- 0 + cr, the field is not read)
   static const bool full_ut = fv3_sw(FV3SW_FXADV_FULL_UT);  // A/B switch
+  const bool standalone = !thin_ut;  // (fv3_fxadv: ut / vt are the caller's arrays; inside d_sw they are scratch, stored on the frame kernel's whole range)
   if (full_ut) thin_ut = false;
   const int isd = 1 - g.nh, ied = g.nx + g.nh, jsd = 1 - g.nh, jed = g.ny + g.nh;
   // Interior kernel, two levels per thread: away from the tile-edge rows / columns the contravariant wind is one
@@ -272,7 +274,7 @@ void fxadv(fv3_ctx *c, fv3_stream_t s, const Real *uc, const Real *vc, Real *crx
     const unsigned p = IX(i, j);
     if (i >= 0 && !int_u) {  // ut on is-1..ie+3, jsd..jed
       const Real utv = f.ut_final(i, j);
-      (ut + b)[p] = utv;
+      if (!standalone || (i >= 1 && i <= g.nx + 1)) (ut + b)[p] = utv;
       if (i >= 1 && i <= g.nx + 1) {
         const Real x = dt * utv;
         Real cr;
@@ -289,7 +291,7 @@ void fxadv(fv3_ctx *c, fv3_stream_t s, const Real *uc, const Real *vc, Real *crx
     }
     if (j >= 0 && !int_v) {  // vt on isd..ied, js-1..je+3
       const Real vtv = f.vt_final(i, j);
-      (vt + b)[p] = vtv;
+      if (!standalone || (j >= 1 && j <= g.ny + 1)) (vt + b)[p] = vtv;
       if (j >= 1 && j <= g.ny + 1) {
         const Real y = dt * vtv;
         Real cr;

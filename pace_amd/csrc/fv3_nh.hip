@@ -665,6 +665,7 @@ extern "C" int fv3_riem_solver_c(fv3_ctx *c, double dt2d, const fv3_field *cappa
   Sim1 sim{g, (Real)c->cst.rdgas, (Real)1.0 / (Real)c->cst.grav, (Real)c->cfg.p_fac, ptop};
   Real *PM = c->scratch[SC_A], *DZ = c->scratch[SC_B], *W2 = c->scratch[SC_C], *PP = c->scratch[SC_D], *GAM = c->scratch[SC_E];
   const int nz = g.nz;
+  if (fv3_sw(FV3SW_DEBUG_FD)) fprintf(stderr, "[riem_solver_c] %s form\n", riem_wave_ok(g) ? "wave" : "column");
   if (riem_wave_ok(g)) {
     const Sim1W sw{g.sk, nz, sim.rgas, sim.rgrav, sim.p_fac, ptop};
     const int i0 = 0, j0 = 0, ni = g.nx + 2, ncol = ni * (g.ny + 2);
@@ -767,6 +768,7 @@ extern "C" int fv3_riem_solver3(fv3_ctx *c, int last_call, double dtd, const fv3
   Real *PM = c->scratch[SC_A], *W2 = c->scratch[SC_C], *PP = c->scratch[SC_D], *GAM = c->scratch[SC_E];
   const int nz = g.nz;
   const bool last = last_call != 0;
+  if (fv3_sw(FV3SW_DEBUG_FD)) fprintf(stderr, "[riem_solver3] %s form\n", riem_wave_ok(g, true) ? "wave" : "column");
   if (riem_wave_ok(g, true)) {
     const Sim1W sw{g.sk, nz, sim.rgas, sim.rgrav, sim.p_fac, ptop};
     const int i0 = 1, j0 = 1, ni = g.nx, ncol = ni * g.ny;
@@ -1295,9 +1297,17 @@ static bool edge_profile_columns(fv3_ctx *c, fv3_stream_t s, const Real *crx, co
                                  Real *yfx_a) {
   static const bool generic = fv3_sw(FV3SW_EDGE_PROFILE_GENERIC);  // A/B switches
   static const bool regs = fv3_sw(FV3SW_EDGE_PROFILE_REG);
-  if (generic) return false;
+  // FV3_DEBUG_FD: which form the level count and the switches select
+  auto say = [](const char *form) {
+    if (fv3_sw(FV3SW_DEBUG_FD)) fprintf(stderr, "[update_dz_d] edge_profile: %s\n", form);
+  };
+  if (generic) {
+    say("generic thread-per-column form");
+    return false;
+  }
   if (!regs && c->g.nz >= 2) {
     static const bool lds = fv3_sw(FV3SW_EDGE_PROFILE_LDS);
+    say(c->g.nz == 79 && !lds ? "wave form, 79 levels" : c->g.nz == 127 && !lds ? "wave form, 127 levels" : sizeof(Real) * c->g.nz * FV3_WAVE <= 64 * 1024 ? "wave form, level count at run time" : "no wave form");
     if (c->g.nz == 79 && !lds) {
       edge_profile_wave<79>(c, s, crx, xfx, cry, yfx, crx_a, xfx_a, cry_a, yfx_a);
       return true;
@@ -1311,6 +1321,7 @@ static bool edge_profile_columns(fv3_ctx *c, fv3_stream_t s, const Real *crx, co
       return true;
     }
   }
+  say(c->g.nz == 79 || c->g.nz == 127 || c->g.nz == 8 ? "register-resident column form" : "generic thread-per-column form");
   switch (c->g.nz) {
     case 79:
       edge_profile_reg<79>(c, s, crx, xfx, cry, yfx, crx_a, xfx_a, cry_a, yfx_a);

@@ -1260,6 +1260,7 @@ void tp2d(fv3_ctx *c, fv3_stream_t s, const Real *q, const Real *crx, const Real
   // FV3_TP2D_MODE = staged | stream (default): the staged form is the reference / A-B path
   static const bool staged = fv3_sw_is(FV3SW_TP2D_MODE, "staged");
   if (k0 > k1) return;
+  if (fv3_sw(FV3SW_DEBUG_FD)) fprintf(stderr, "[fv_tp_2d] %s form, levels %d..%d\n", staged ? "staged" : "marching", k0, k1);
   if (!staged) {
     tp2d_stream(c, s, q, crx, cry, xfx, yfx, fx, fy, mfx, mfy, mass, hord, dn, k0, k1, epi);
     return;
