@@ -24,6 +24,7 @@
 
 #include "../../include/fv3_mi355x.h"
 #include "fv3_switch.h"
+#include "fv3_box.h"  // Box, Frame, the tile-edge flags FV3_W / E / S / N
 
 #ifdef FV3_HOST_EMU
 #define FV3_HD
@@ -155,11 +156,6 @@ FV3_HD inline void fv3_store_el(Real *base, unsigned idx, Real *sink, bool owned
 #define FV3_SCHED_FENCE() ((void)0)
 #endif
 
-#define FV3_W 1
-#define FV3_E 2
-#define FV3_S 4
-#define FV3_N 8
-
 // Geometry + metric terms, captured by value in every stage lambda.
 // 2-D metric terms (immutable after context creation).  Addressing them through the constant
 // address space (address_space(4)) lets the compiler hoist them out of the level loop of launch3,
@@ -199,10 +195,6 @@ struct Geo {
 
 // storage offset of Fortran-local (i, j) inside one k-plane
 #define IX(i, j) ((unsigned)(((j) + g.o) * g.sj32 + ((i) + g.o)))
-
-struct Box {
-  int i0, i1, j0, j1, k0, k1;  // inclusive; i, j Fortran-local; k 0-based
-};
 
 // per-level coefficient tables precomputed on the host at context creation (device arrays [nz+1])
 struct DampTables {
@@ -518,9 +510,6 @@ inline void launch3(const fv3_ctx *c, fv3_stream_t s, Box b, F f) {
 // w[2], w[3] (S / N: the usual 64 x 4 workgroups).  k runs over b.k0 .. b.k1 of
 // w[0] (the level chunks).  ONE launch for the four windows (round 6); FV3_FRAME_LAUNCH=split: one launch per window (rounds 3 - 5, A/B).
 // ---------------------------------------------------------------------------------------------
-struct Frame {
-  Box w[4];
-};
 #ifndef FV3_HOST_EMU
 // narrow windows (a few columns wide): a workgroup is 8 columns x 32 rows, so a wave reads 8 rows of 64 contiguous bytes (lanes
 // along j -- the transposed form -- made every lane of a load its own 128-byte line: 6 x the time of an S / N window of equal size)

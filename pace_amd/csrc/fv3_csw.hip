@@ -9,7 +9,10 @@
 // Default form: ONE marching wave kernel does all five stages on the interior rectangle of every sub-domain (csw_fused_stream);
 // the generic per-point stage kernels at the end of this file finish the windows along the sub-domain boundary, where the
 // tile-edge formulas live.  FV3_CSW_MARCH=abc / =0 and FV3_CSW_B_GENERIC select the earlier forms (bitwise equal, A/B tests).
+// Layout: the two marches, then csw_plan() -- EVERY decision of one call, taken before its first launch -- the stage functions, which take the plan by const
+// reference and decide nothing, and fv3_c_sw, which strings them together.  Who owns which point, and the windows' boxes: fv3_csw_plan.h.
 #include "fv3_ops.h"
+#include "fv3_csw_plan.h"
 
 #define CSW_A1 ((Real)0.5625)
 #define CSW_A2 ((Real)-0.0625)
@@ -69,6 +72,24 @@ FV3_HD inline Real edge_interp4(Real u1, Real u2, Real u3, Real u4, Real d1, Rea
 
 }  // namespace
 
+// The operator's fields (checked by fv3_c_sw) and its two scratch fields: ke = SC_A, vort = SC_B.
+struct CswFields {
+  Real *delp, *pt, *u, *v, *w, *uc, *vc, *ua, *va, *ut, *vt, *divgd, *omga, *delpc, *ptc, *ke, *vort;
+  Real dt2;
+};
+// What csw_plan() decides (the switches and forms: there).
+struct CswPlan {
+  int form;            // CswForm: what the stage kernels' owner tests and the window table (fv3_csw_plan.h) take
+  const char *report;  // FV3_DEBUG_FD: the form in words (else null)
+  int KC, nkc;         // levels one thread of the stage kernels walks, and the chunks of them
+  bool do_div;         // nord > 0: c_sw forms the corner divergence
+  bool uava_thin;      // the fused march stores ua / va only where somebody reads them (fv3_seq_hints::uava_thin)
+  // streams: the stage A / B windows' (the auxiliary one beside the fused march, else the caller's: EV_FORK .. EV_WIN_JOIN), the stage D / E windows' (the
+  // auxiliary one with defer: EV_CSW_LATE_FORK, and the join EV_CSW_LATE_JOIN is left to the sequencer, fv3_csw_join)
+  fv3_stream_t s_ab, s_de;
+  bool defer;
+};
+
 // ---------------------------------------------------------------------------------------------
 // Stages A + B + C on the interior rectangle of every sub-domain as ONE marching wave kernel.
 // The three stages read nothing but (u, v): utmp (4-point in j) lives in a 4-row register window of u, vtmp
@@ -94,20 +115,12 @@ FV3_HD inline Real edge_interp4(Real u1, Real u2, Real u3, Real u4, Real d1, Rea
 #define CSW_LANES(vl, l) FV3_VLANES(CSW_CPL, blk, vl, l)
 #define CSW_SHR(K, arr) FV3_VSHR(CSW_CPL, K, arr, l, vl)
 #define CSW_SHL(K, arr) FV3_VSHL(CSW_CPL, K, arr, l, vl)
-struct CswRect {
-  int i_lo, i_hi, j_lo, j_hi;
-};
-FV3_HD inline CswRect csw_rect(int fl, int nx, int ny, int npx, int npy) {
-  CswRect r;
-  r.i_lo = (fl & FV3_W) ? 6 : 0;
-  r.i_hi = (fl & FV3_E) ? npx - 5 : nx + 1;
-  r.j_lo = (fl & FV3_S) ? 6 : 0;
-  r.j_hi = (fl & FV3_N) ? npy - 5 : ny + 1;
-  return r;
-}
 
-static void csw_abc_stream(fv3_ctx *c, fv3_stream_t s, const Real *u, const Real *v, Real *ua, Real *va, Real *uc, Real *vc, Real *ut, Real *vt, Real *divgd,
-                           Real dt2, bool do_div) {
+static void csw_abc_stream(fv3_ctx *c, fv3_stream_t s, const CswPlan &pl, const CswFields &f) {
+  const Real *u = f.u, *v = f.v;
+  Real *ua = f.ua, *va = f.va, *uc = f.uc, *vc = f.vc, *ut = f.ut, *vt = f.vt, *divgd = f.divgd;
+  const Real dt2 = f.dt2;
+  const bool do_div = pl.do_div;
   const Geo g = c->g;
   const Geo *gp = c->g_dev;
   const int nk = g.nz;
@@ -305,8 +318,9 @@ static void csw_abc_stream(fv3_ctx *c, fv3_stream_t s, const Real *u, const Real
 // The intermediate C-grid winds uc0 / vc0, the kinetic energy and the corner vorticity live in the march: step R loads row R
 // and finishes, in this order, ua / va / uc0 / ut / the divergence / the upwind transport / ke / the vorticity of row R-2
 // and vc0 / vt of row R-1 (as csw_abc_stream), the time-centred vc of row R-2 and the time-centred uc of row R-3 (which
-// needs the vorticity of the row above).  Regions, with R0 = [i_lo, i_hi] x [j_lo, j_hi] the interior rectangle:
-//   ua va ut vt           R0                              divgd   corners of R0 from (1, 1)
+// needs the vorticity of the row above).  Regions, with R0 = [i_lo, i_hi] x [j_lo, j_hi] the interior rectangle (the predicates csw_R0, csw_RC, csw_RD, csw_VR,
+// csw_RE of fv3_csw_plan.h, which the stage kernels ask and tests/test_c_sw_plan.py checks against the windows; the march's own lane / row masks spell them out):
+//   ua va ut vt           R0                              divgd   RC = corners of R0 from (1, 1)
 //   delpc ptc omga, ke    RD = R0 minus its last column / row (the east / north face values come from the neighbour)
 //   vorticity             VR = corners of R0 from (i_lo + 1, j_lo + 1)
 //   final uc / vc         RE = R0 minus a one-cell rim (ke of the cell to the west / south, vorticity of the corner above)
@@ -329,8 +343,11 @@ static void csw_abc_stream(fv3_ctx *c, fv3_stream_t s, const Real *u, const Real
 #define CSWF_ST(ptr, val) (*(ptr) = (val))
 #define CSWF_STE(base, idx, val) (FV3_EL(base, idx) = (val))
 #endif
-static void csw_fused_stream(fv3_ctx *c, fv3_stream_t s, const Real *u, const Real *v, const Real *delp, const Real *pt, const Real *w, Real *ua, Real *va, Real *uc,
-                             Real *vc, Real *ut, Real *vt, Real *divgd, Real *delpc, Real *ptc, Real *omga, Real *ke, Real *vort, Real dt2, bool do_div, bool uava_thin) {
+static void csw_fused_stream(fv3_ctx *c, fv3_stream_t s, const CswPlan &pl, const CswFields &f) {
+  const Real *u = f.u, *v = f.v, *delp = f.delp, *pt = f.pt, *w = f.w;
+  Real *ua = f.ua, *va = f.va, *uc = f.uc, *vc = f.vc, *ut = f.ut, *vt = f.vt, *divgd = f.divgd, *delpc = f.delpc, *ptc = f.ptc, *omga = f.omga, *ke = f.ke, *vort = f.vort;
+  const Real dt2 = f.dt2;
+  const bool do_div = pl.do_div, uava_thin = pl.uava_thin;
   const Geo g = c->g;
   const Geo *gp = c->g_dev;
   const int nk = g.nz;
@@ -675,49 +692,68 @@ static void csw_fused_stream(fv3_ctx *c, fv3_stream_t s, const Real *u, const Re
   });
 }
 
-extern "C" int fv3_c_sw(fv3_ctx *c, const fv3_field *delp_, const fv3_field *pt_, const fv3_field *u_, const fv3_field *v_, const fv3_field *w_,
-                        const fv3_field *uc_, const fv3_field *vc_, const fv3_field *ua_, const fv3_field *va_, const fv3_field *ut_, const fv3_field *vt_,
-                        const fv3_field *divgd_, const fv3_field *omga_, const fv3_field *delpc_, const fv3_field *ptc_, double dt2d, void *stream) {
-  if (!c) return FV3_ERR_ARG;
-  FV3_FIELD(delp, delp_) FV3_FIELD(pt, pt_) FV3_FIELD(u, u_) FV3_FIELD(v, v_) FV3_FIELD(w, w_) FV3_FIELD(uc, uc_) FV3_FIELD(vc, vc_)
-  FV3_FIELD(ua, ua_) FV3_FIELD(va, va_) FV3_FIELD(ut, ut_) FV3_FIELD(vt, vt_) FV3_FIELD(divgd, divgd_) FV3_FIELD(omga, omga_)
-  FV3_FIELD(delpc, delpc_) FV3_FIELD(ptc, ptc_)
-  const Geo g = c->g;
-  fv3_stream_t s = (fv3_stream_t)stream;
-  const Real dt2 = (Real)dt2d;
-  const int nz1 = g.nz - 1;
-  const int nord = c->cfg.nord;
-  Real *ke = c->scratch[SC_A], *vort = c->scratch[SC_B];
-
-  // (A) contravariant A-grid winds on is-2..ie+2
-  // Where stage B's two-row interior kernel runs (below) it also produces ua / va -- it holds utmp(i, j) and vtmp(i, j)
-  // of its points anyway -- so this per-point form then only covers the boundary windows and the outer ring.
-  // A/B switches, same results: FV3_CSW_B_GENERIC: every point by the generic per-point stage kernels; FV3_CSW_MARCH=0: the round-1
-  // form (two-row stage-B kernel on the interior rectangle, the other stages as full stage kernels); FV3_CSW_MARCH=abc: stages
-  // A - C of the interior as a marching kernel, D and E as stage kernels; default: the whole interior as one marching kernel
+// ---------------------------------------------------------------------------------------------
+// c_sw: plan, stages, streams (as d_sw: fv3_dsw.hip).  csw_plan() takes every decision of one call before its first launch or event -- from the sub-domain's
+// size, the sequencer's hints (c->seq), the switch table and whether an auxiliary stream exists -- and launches nothing; it is the only reader of the switch
+// table in this file.  The stages decide nothing.  Geometry (who owns a point, where the windows lie): fv3_csw_plan.h.
+// A/B switches, same results: FV3_CSW_B_GENERIC: every point by the generic per-point stage kernels; FV3_CSW_MARCH=0: the round-1
+// form (two-row stage-B kernel on the interior rectangle, the other stages as full stage kernels); FV3_CSW_MARCH=abc: stages
+// A - C of the interior as a marching kernel, D and E as stage kernels; default: the whole interior as one marching kernel
+// ---------------------------------------------------------------------------------------------
+static CswPlan csw_plan(const fv3_ctx *c, fv3_stream_t s) {
+  const Geo &g = c->g;
+  CswPlan pl{};
   const bool b_split = g.nx >= 16 && g.ny >= 16 && !fv3_sw(FV3SW_CSW_B_GENERIC);
   const int march_env = fv3_sw(FV3SW_CSW_MARCH);  // (0 default, 1 "0", 2 "abc")
-  const bool march = b_split && march_env != 1;
-  const bool fused = march && march_env != 2;
-  if (fv3_sw(FV3SW_DEBUG_FD))
-    fprintf(stderr, "[c_sw] %s\n", !b_split ? "generic per-point stage kernels everywhere" : fused ? "interior as one march" : march ? "stages A - C as a march" : "two-row stage-B kernel on the interior");
+  const int form = !b_split ? CSW_GENERIC : march_env == 1 ? CSW_TWO_ROW : march_env == 2 ? CSW_ABC : CSW_FUSED;
+  const bool fused = form == CSW_FUSED;
+  static const char *const words[] = {"generic per-point stage kernels everywhere", "two-row stage-B kernel on the interior", "stages A - C as a march", "interior as one march"};
+  pl.form = form;
+  pl.report = fv3_sw(FV3SW_DEBUG_FD) ? words[form] : nullptr;
   // levels one thread of the stage kernels walks (the metric terms of its point are read once for them): FV3_KC for launches
-  // over whole sub-domains; 2 when they only cover the boundary windows, which are too few points to fill the chip otherwise
-  static const int win_kc = fv3_sw(FV3SW_CSW_WIN_KC);
-  const int KC = fused ? win_kc : FV3_KC;
-  const int nkc = (nz1 + KC) / KC;
-  // interior rectangle of sub-domain t: columns [i_lo, i_hi], rows [j_lo, j_hi] (the two-row kernel needs an even row count)
-  auto b_rect = [=] FV3_HD(int fl) {
-    CswRect r = csw_rect(fl, g.nx, g.ny, g.npx, g.npy);
-    if (!march) r.j_hi = r.j_lo + 2 * ((r.j_hi - r.j_lo + 1) / 2) - 1;
-    return r;
-  };
-  auto stage_a = [=] FV3_HD(int t, int kp, int i, int j) {
+  // over whole sub-domains; FV3_CSW_WIN_KC (2) when they only cover the boundary windows, which are too few points to fill the chip otherwise
+  const int win_kc = fv3_sw(FV3SW_CSW_WIN_KC);
+  pl.KC = fused ? win_kc : FV3_KC;
+  pl.nkc = (g.nz - 1 + pl.KC) / pl.KC;
+  pl.do_div = c->cfg.nord > 0;
+  // (FV3_SEQ_UAVA=every: ua / va stored in full by every sub-step, A/B; read per call)
+  pl.uava_thin = c->seq.uava_thin && !fv3_sw_is(FV3SW_SEQ_UAVA, "every");
+  // Round 5: the boundary windows of stages A and B read u / v (and, within two cells of a tile edge, the window's own ua / va) and write
+  // window cells only; the interior march reads the five inputs and writes interior cells only.  Neither waits for the other, so the eight
+  // small window launches (1.0 ms of a few dozen waves each) go to the auxiliary stream and run BESIDE the march; stage C -- whose windows
+  // read the march's ut / vt across the rim -- joins them.  FV3_CSW_WIN_OVERLAP=0: in program order (A/B; same values).  Events 0 = fork, 1 = join.
+  const bool win_overlap = fv3_sw(FV3SW_CSW_WIN_OVERLAP);
+  pl.s_ab = (fused && win_overlap) ? fv3_aux(c, s) : s;
+  // Round 6, FV3_CSW_DEFER=1 (measured, NOT the default: R6-11): inside the sequencer the eight window launches of stages D and E (1.15 ms of small launches behind
+  // the march) go to the auxiliary stream and the operator returns without waiting for them: update_dz_c, which follows, reads ut / vt / zh only, and
+  // riem_solver_c -- the first reader of the windows' delpc / ptc / wc -- is where the sequencer joins (fv3_csw_join).  Same values; c_sw shrinks by 1.1 ms and
+  // update_dz_c, bandwidth-bound beside the windows, grows by 0.85: four same-box pairs gave -0.7 / -0.0 / +0.6 / +0.1 ms per sub-step.  Events 6 = fork, 7 = join.
+  const bool defer_on = fv3_sw(FV3SW_CSW_DEFER);
+  pl.s_de = (fused && defer_on && c->seq.csw_defer) ? fv3_aux(c, s) : s;
+  pl.defer = pl.s_de != s;
+  return pl;
+}
+
+// what every stage launch does: the four windows where the form has an interior kernel for the stage, else the stage's whole domain box
+template <class F>
+static void csw_launch(fv3_ctx *c, fv3_stream_t s, const CswPlan &pl, int stage, F body) {
+  if (csw_framed(pl.form, stage))
+    launch_frame(c, s, csw_frame(stage, c->g.nx, c->g.ny, pl.nkc), body);  // (launch_frame: W / E as narrow 8 x 32 workgroups, S / N as they lie)
+  else
+    launch3(c, s, csw_domain(stage, c->g.nx, c->g.ny, pl.nkc), body);
+}
+
+// (A) contravariant A-grid winds on is-2..ie+2
+// Where stage B's two-row interior kernel runs (below) it also produces ua / va -- it holds utmp(i, j) and vtmp(i, j)
+// of its points anyway -- so this per-point form then only covers the boundary windows and the outer ring.
+static void csw_stage_a(fv3_ctx *c, fv3_stream_t s, const CswPlan &pl, const CswFields &f) {
+  const Geo g = c->g;
+  const CswGeom gm = csw_geom(g.nx, g.ny, g.npx, g.npy, pl.form, CSW_ST_A);
+  const int KC = pl.KC, nz1 = g.nz - 1;
+  Real *u = f.u, *v = f.v, *ua = f.ua, *va = f.va;
+  csw_launch(c, s, pl, CSW_ST_A, [=] FV3_HD(int t, int kp, int i, int j) {
     const int fl = g.flags[t];
-    if (b_split) {
-      const CswRect rc = b_rect(fl);
-      if (i >= rc.i_lo && i <= rc.i_hi && j >= rc.j_lo && j <= rc.j_hi) return;  // done by the interior kernel
-    }
+    if (csw_interior_owns(gm, CSW_ST_A, fl, i, j)) return;  // done by the interior kernel
     const long m2 = t * g.st2;
     const unsigned p = IX(i, j);
     const Real cs = (g.cosa_s + m2)[p], rs2 = (g.rsin2 + m2)[p];
@@ -731,119 +767,109 @@ extern "C" int fv3_c_sw(fv3_ctx *c, const fv3_field *delp_, const fv3_field *pt_
       (ua + b)[p] = (ut_ - vt_ * cs) * rs2;
       (va + b)[p] = (vt_ - ut_ * cs) * rs2;
     }
-  };
-  // Round 5: the boundary windows of stages A and B read u / v (and, within two cells of a tile edge, the window's own ua / va) and write
-  // window cells only; the interior march reads the five inputs and writes interior cells only.  Neither waits for the other, so the eight
-  // small window launches (1.0 ms of a few dozen waves each) go to the auxiliary stream and run BESIDE the march; stage C -- whose windows
-  // read the march's ut / vt across the rim -- joins them.  FV3_CSW_WIN_OVERLAP=0: in program order (A/B; same values).  Events 0 = fork, 1 = join.
-  static const bool win_overlap = fv3_sw(FV3SW_CSW_WIN_OVERLAP);
-  fv3_stream_t sw_ = (fused && b_split && win_overlap) ? fv3_aux(c, s) : s;
-  if (sw_ != s) {
-    fv3_signal(c, s, EV_FORK);
-    fv3_wait(c, sw_, EV_FORK);
-  }
-  if (b_split) {
-    // the four windows along the sub-domain boundary (launch_frame: W / E as narrow 8 x 32 workgroups, S / N as they lie)
-    const int e0 = g.nx - 3;
-    launch_frame(c, sw_, Frame{{Box{-1, 5, -1, g.ny + 2, 0, nkc - 1}, Box{e0, e0 + 5, -1, g.ny + 2, 0, 0}, Box{6, g.nx - 4, -1, 5, 0, 0}, Box{6, g.nx - 4, g.ny - 4, g.ny + 2, 0, 0}}}, stage_a);
-  } else {
-    launch3(c, s, Box{-1, g.nx + 2, -1, g.ny + 2, 0, nkc - 1}, stage_a);
-  }
+  });
+}
 
-  // (B) C-grid winds + contravariant ut, vt (already scaled: dt2 * ut * dy * sin_sg)
-  // The generic per-point form does 32 u / v loads per point and is bound by them (halving them in a timing
-  // experiment took 2.5 ms off c_sw).  Points whose whole stencil uses the interior formulas are therefore done by
-  // a lean kernel in which a thread owns TWO rows and shares the utmp / vtmp rows between them (20 loads per point);
-  // the generic form then only runs on four windows along the sub-domain boundary (and skips the interior).
-  if (fused) {
-    // (FV3_SEQ_UAVA=every: ua / va stored in full by every sub-step, A/B; read per call)
-    csw_fused_stream(c, s, u, v, delp, pt, w, ua, va, uc, vc, ut, vt, divgd, delpc, ptc, omga, ke, vort, dt2, nord > 0, c->seq.uava_thin && !fv3_sw_is(FV3SW_SEQ_UAVA, "every"));
-  } else if (march) {
-    csw_abc_stream(c, s, u, v, ua, va, uc, vc, ut, vt, divgd, dt2, nord > 0);
-  } else if (b_split) {
-    launch3(c, s, Box{0, g.nx + 1, 0, (g.ny + 2) / 2, 0, nkc - 1}, [=] FV3_HD(int t, int kp, int i_, int jp) {
-      const CswRect rc = b_rect(g.flags[t]);
-      if (i_ < rc.i_lo || i_ > rc.i_hi || jp >= (rc.j_hi - rc.j_lo + 1) / 2) return;
-      const long m2 = t * g.st2;
-      int i = i_, j = rc.j_lo + 2 * jp;
-      const int j_base = j;
-      // metric terms of the two points, shared by the levels of the chunk
-      Real mcu[2], mru[2], mdy[2], ms3[2], ms1[2], mcv[2], mrv[2], mdx[2], ms4[2], ms2[2], mcs[2], mr2[2];
+// (B) C-grid winds + contravariant ut, vt (already scaled: dt2 * ut * dy * sin_sg)
+// The generic per-point form does 32 u / v loads per point and is bound by them (halving them in a timing
+// experiment took 2.5 ms off c_sw).  Points whose whole stencil uses the interior formulas are therefore done by
+// a lean kernel in which a thread owns TWO rows and shares the utmp / vtmp rows between them (20 loads per point);
+// the generic form then only runs on four windows along the sub-domain boundary (and skips the interior).
+static void csw_two_row_b(fv3_ctx *c, fv3_stream_t s, const CswPlan &pl, const CswFields &f) {
+  const Geo g = c->g;
+  const CswGeom gm = csw_geom(g.nx, g.ny, g.npx, g.npy, pl.form, CSW_ST_B);
+  const int KC = pl.KC, nz1 = g.nz - 1;
+  Real *u = f.u, *v = f.v, *ua = f.ua, *va = f.va, *uc = f.uc, *vc = f.vc, *ut = f.ut, *vt = f.vt;
+  const Real dt2 = f.dt2;
+  launch3(c, s, Box{0, g.nx + 1, 0, (g.ny + 2) / 2, 0, pl.nkc - 1}, [=] FV3_HD(int t, int kp, int i_, int jp) {
+    const CswRect rc = gm.rect(g.flags[t]);  // (csw_even_rows: a thread owns two rows)
+    if (i_ < rc.i_lo || i_ > rc.i_hi || jp >= (rc.j_hi - rc.j_lo + 1) / 2) return;
+    const long m2 = t * g.st2;
+    int i = i_, j = rc.j_lo + 2 * jp;
+    const int j_base = j;
+    // metric terms of the two points, shared by the levels of the chunk
+    Real mcu[2], mru[2], mdy[2], ms3[2], ms1[2], mcv[2], mrv[2], mdx[2], ms4[2], ms2[2], mcs[2], mr2[2];
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      const unsigned q = IX(i, j + r);
+      mcu[r] = (g.cosa_u + m2)[q];
+      mru[r] = (g.rsin_u + m2)[q];
+      mdy[r] = (g.dy + m2)[q];
+      ms3[r] = (g.sin_sg3 + m2)[IX(i - 1, j + r)];
+      ms1[r] = (g.sin_sg1 + m2)[q];
+      mcv[r] = (g.cosa_v + m2)[q];
+      mrv[r] = (g.rsin_v + m2)[q];
+      mdx[r] = (g.dx + m2)[q];
+      ms4[r] = (g.sin_sg4 + m2)[IX(i, j + r - 1)];
+      ms2[r] = (g.sin_sg2 + m2)[q];
+      mcs[r] = (g.cosa_s + m2)[q];
+      mr2[r] = (g.rsin2 + m2)[q];
+    }
+#pragma unroll 1
+    for (int kk = 0; kk < KC; ++kk) {
+      const int k = KC * kp + kk;
+      if (k > nz1) break;
+      i = i_;
+      j = j_base;
+      FV3_LAUNDER(i);
+      FV3_LAUNDER(j);
+      const long b = t * g.st + k * g.sk;
+      const Real *ul = u + b, *vl = v + b;
+      // utmp at columns i-2 .. i+1 for the two rows: five u rows j-1 .. j+3 per column
+      Real ut_[4][2], uc0[2] = {(Real)0, (Real)0};  // uc0: u(i, j + r) for the v part
+#pragma unroll
+      for (int a = 0; a < 4; ++a) {
+        const int ii = i - 2 + a;
+        const Real um = ul[IX(ii, j - 1)], u0 = ul[IX(ii, j)], u1 = ul[IX(ii, j + 1)], u2 = ul[IX(ii, j + 2)], u3 = ul[IX(ii, j + 3)];
+        ut_[a][0] = CSW_A2 * (um + u2) + CSW_A1 * (u0 + u1);
+        ut_[a][1] = CSW_A2 * (u0 + u3) + CSW_A1 * (u1 + u2);
+        if (a == 2) {
+          uc0[0] = u0;
+          uc0[1] = u1;
+        }
+      }
+      // vtmp at rows j-2 .. j+2: four v columns i-1 .. i+2 per row
+      Real vt_[5], vc0[2] = {(Real)0, (Real)0};  // vc0: v(i, j + r) for the u part
+#pragma unroll
+      for (int a = 0; a < 5; ++a) {
+        const int jj = j - 2 + a;
+        const Real vm = vl[IX(i - 1, jj)], v0 = vl[IX(i, jj)], v1 = vl[IX(i + 1, jj)], v2 = vl[IX(i + 2, jj)];
+        vt_[a] = CSW_A2 * (vm + v2) + CSW_A1 * (v0 + v1);
+        if (a == 2) vc0[0] = v0;
+        if (a == 3) vc0[1] = v0;
+      }
 #pragma unroll
       for (int r = 0; r < 2; ++r) {
-        const unsigned q = IX(i, j + r);
-        mcu[r] = (g.cosa_u + m2)[q];
-        mru[r] = (g.rsin_u + m2)[q];
-        mdy[r] = (g.dy + m2)[q];
-        ms3[r] = (g.sin_sg3 + m2)[IX(i - 1, j + r)];
-        ms1[r] = (g.sin_sg1 + m2)[q];
-        mcv[r] = (g.cosa_v + m2)[q];
-        mrv[r] = (g.rsin_v + m2)[q];
-        mdx[r] = (g.dx + m2)[q];
-        ms4[r] = (g.sin_sg4 + m2)[IX(i, j + r - 1)];
-        ms2[r] = (g.sin_sg2 + m2)[q];
-        mcs[r] = (g.cosa_s + m2)[q];
-        mr2[r] = (g.rsin2 + m2)[q];
+        const unsigned p = IX(i, j + r);
+        {  // stage A's ua / va of the point: utmp(i, j) and vtmp(i, j) are at hand
+          const Real ut0 = ut_[2][r], vt0 = vt_[2 + r];
+          (ua + b)[p] = (ut0 - vt0 * mcs[r]) * mr2[r];
+          (va + b)[p] = (vt0 - ut0 * mcs[r]) * mr2[r];
+        }
+        const Real ucv = CSW_A2 * (ut_[0][r] + ut_[3][r]) + CSW_A1 * (ut_[1][r] + ut_[2][r]);
+        const Real utv = (ucv - vc0[r] * mcu[r]) * mru[r];
+        (uc + b)[p] = ucv;
+        (ut + b)[p] = utv > (Real)0 ? dt2 * utv * mdy[r] * ms3[r] : dt2 * utv * mdy[r] * ms1[r];
+        const Real vcv = CSW_A2 * (vt_[r] + vt_[r + 3]) + CSW_A1 * (vt_[r + 1] + vt_[r + 2]);
+        const Real vtv = (vcv - uc0[r] * mcv[r]) * mrv[r];
+        (vc + b)[p] = vcv;
+        (vt + b)[p] = vtv > (Real)0 ? dt2 * vtv * mdx[r] * ms4[r] : dt2 * vtv * mdx[r] * ms2[r];
       }
-#pragma unroll 1
-      for (int kk = 0; kk < KC; ++kk) {
-        const int k = KC * kp + kk;
-        if (k > nz1) break;
-        i = i_;
-        j = j_base;
-        FV3_LAUNDER(i);
-        FV3_LAUNDER(j);
-        const long b = t * g.st + k * g.sk;
-        const Real *ul = u + b, *vl = v + b;
-        // utmp at columns i-2 .. i+1 for the two rows: five u rows j-1 .. j+3 per column
-        Real ut_[4][2], uc0[2] = {(Real)0, (Real)0};  // uc0: u(i, j + r) for the v part
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-          const int ii = i - 2 + a;
-          const Real um = ul[IX(ii, j - 1)], u0 = ul[IX(ii, j)], u1 = ul[IX(ii, j + 1)], u2 = ul[IX(ii, j + 2)], u3 = ul[IX(ii, j + 3)];
-          ut_[a][0] = CSW_A2 * (um + u2) + CSW_A1 * (u0 + u1);
-          ut_[a][1] = CSW_A2 * (u0 + u3) + CSW_A1 * (u1 + u2);
-          if (a == 2) {
-            uc0[0] = u0;
-            uc0[1] = u1;
-          }
-        }
-        // vtmp at rows j-2 .. j+2: four v columns i-1 .. i+2 per row
-        Real vt_[5], vc0[2] = {(Real)0, (Real)0};  // vc0: v(i, j + r) for the u part
-#pragma unroll
-        for (int a = 0; a < 5; ++a) {
-          const int jj = j - 2 + a;
-          const Real vm = vl[IX(i - 1, jj)], v0 = vl[IX(i, jj)], v1 = vl[IX(i + 1, jj)], v2 = vl[IX(i + 2, jj)];
-          vt_[a] = CSW_A2 * (vm + v2) + CSW_A1 * (v0 + v1);
-          if (a == 2) vc0[0] = v0;
-          if (a == 3) vc0[1] = v0;
-        }
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-          const unsigned p = IX(i, j + r);
-          {  // stage A's ua / va of the point: utmp(i, j) and vtmp(i, j) are at hand
-            const Real ut0 = ut_[2][r], vt0 = vt_[2 + r];
-            (ua + b)[p] = (ut0 - vt0 * mcs[r]) * mr2[r];
-            (va + b)[p] = (vt0 - ut0 * mcs[r]) * mr2[r];
-          }
-          const Real ucv = CSW_A2 * (ut_[0][r] + ut_[3][r]) + CSW_A1 * (ut_[1][r] + ut_[2][r]);
-          const Real utv = (ucv - vc0[r] * mcu[r]) * mru[r];
-          (uc + b)[p] = ucv;
-          (ut + b)[p] = utv > (Real)0 ? dt2 * utv * mdy[r] * ms3[r] : dt2 * utv * mdy[r] * ms1[r];
-          const Real vcv = CSW_A2 * (vt_[r] + vt_[r + 3]) + CSW_A1 * (vt_[r + 1] + vt_[r + 2]);
-          const Real vtv = (vcv - uc0[r] * mcv[r]) * mrv[r];
-          (vc + b)[p] = vcv;
-          (vt + b)[p] = vtv > (Real)0 ? dt2 * vtv * mdx[r] * ms4[r] : dt2 * vtv * mdx[r] * ms2[r];
-        }
-      }
-    });
-  }
-  auto stage_b = [=] FV3_HD(int t, int kp, int i_, int j_) {
-    const int fl = g.flags[t];
-    if (b_split) {
-      const CswRect rc = b_rect(fl);
-      if (i_ >= rc.i_lo && i_ <= rc.i_hi && j_ >= rc.j_lo && j_ <= rc.j_hi) return;  // done by the interior kernel
     }
+  });
+}
+
+// stage B, generic per-point form: every tile-edge clause of the A -> C interpolation
+static void csw_stage_b(fv3_ctx *c, fv3_stream_t s, const CswPlan &pl, const CswFields &f) {
+  const Geo g = c->g;
+  const CswGeom gm = csw_geom(g.nx, g.ny, g.npx, g.npy, pl.form, CSW_ST_B);
+  const int KC = pl.KC, nz1 = g.nz - 1;
+  Real *u = f.u, *v = f.v, *ua = f.ua, *va = f.va, *uc = f.uc, *vc = f.vc, *ut = f.ut, *vt = f.vt;
+  const Real dt2 = f.dt2;
+  // (on windows: one right-sized launch_frame -- launch3w would size every window's grid for the largest one; the 6-column W / E windows run as 8-column x 32-row workgroups)
+  csw_launch(c, s, pl, CSW_ST_B, [=] FV3_HD(int t, int kp, int i_, int j_) {
+    const int fl = g.flags[t];
+    if (csw_interior_owns(gm, CSW_ST_B, fl, i_, j_)) return;  // done by the interior kernel
     const long m2 = t * g.st2;
     const bool W = fl & FV3_W, E = fl & FV3_E, S = fl & FV3_S, N = fl & FV3_N;
     const int npx = g.npx, npy = g.npy;
@@ -950,25 +976,14 @@ extern "C" int fv3_c_sw(fv3_ctx *c, const fv3_field *delp_, const fv3_field *pt_
       (vt + b)[p] = vtv > (Real)0 ? dt2 * vtv * m_dx * m_s4s : dt2 * vtv * m_dx * m_s2;
     }
     }
-  };
-  {
-    const Box nat{0, g.nx + 2, 0, g.ny + 2, 0, nkc - 1};
-    if (b_split) {
-      // (one right-sized launch per window: launch3w sizes every window's grid for the largest one)
-      // (the 6-column W / E windows run as 8-column x 32-row workgroups: launch_frame)
-      const int e0 = g.nx - 3;
-      launch_frame(c, sw_, Frame{{Box{0, 5, 0, g.ny + 2, 0, nkc - 1}, Box{e0, e0 + 5, 0, g.ny + 2, 0, 0}, Box{6, g.nx - 4, 0, 5, 0, 0}, Box{6, g.nx - 4, g.ny - 4, g.ny + 2, 0, 0}}}, stage_b);
-    } else {
-      launch3(c, s, nat, stage_b);
-    }
-  }
-  if (sw_ != s) {
-    fv3_signal(c, sw_, EV_WIN_JOIN);
-    fv3_wait(c, s, EV_WIN_JOIN);
-  }
+  });
+}
 
-  // the in-place corner fixes of ua / va the reference leaves behind (checkpointed as uad / vad)
-  launch3(c, s, Box{1, 1, 1, 1, 0, nz1}, [=] FV3_HD(int t, int k, int, int) {
+// the in-place corner fixes of ua / va the reference leaves behind (checkpointed as uad / vad)
+static void csw_uava_corners(fv3_ctx *c, fv3_stream_t s, const CswPlan &, const CswFields &f) {
+  const Geo g = c->g;
+  Real *ua = f.ua, *va = f.va;
+  launch3(c, s, Box{1, 1, 1, 1, 0, g.nz - 1}, [=] FV3_HD(int t, int k, int, int) {
     const int fl = g.flags[t];
     const long b = t * g.st + k * g.sk;
     const bool W = fl & FV3_W, E = fl & FV3_E, S = fl & FV3_S, N = fl & FV3_N;
@@ -993,95 +1008,97 @@ extern "C" int fv3_c_sw(fv3_ctx *c, const fv3_field *delp_, const fv3_field *pt_
     if (E && N) { vaa[IX(npx, npy)] = n_va[4]; vaa[IX(npx, npy + 1)] = n_va[5]; }
     if (W && N) { vaa[IX(0, npy)] = n_va[6]; vaa[IX(0, npy + 1)] = n_va[7]; }
   });
+}
 
-  // (C) divergence on corners.  Two levels per thread: the ten metric terms of a corner are read once and
-  // used for both levels (they are 2/3 of this kernel's bytes).
-  if (nord > 0) {
-    const int npair = (nz1 + KC) / KC;
-    auto stage_c = [=] FV3_HD(int t, int kp, int i, int j) {
-      const int fl = g.flags[t];
-      if (march) {  // the corners whose 2 x 2 block of ua / va the marching kernel holds are done there
-        const CswRect rc = b_rect(fl);
-        if (i >= rc.i_lo && i >= 1 && i <= rc.i_hi && j >= rc.j_lo && j >= 1 && j <= rc.j_hi) return;
-      }
-      const long m2 = t * g.st2;
-      const bool W = fl & FV3_W, E = fl & FV3_E, S = fl & FV3_S, N = fl & FV3_N;
-      const int npx = g.npx, npy = g.npy;
-      // metric factors of the four faces around the corner (exactly the sub-expressions of the one-level form)
-      struct Face {
-        Real cs, f;  // cos sum, dyc * 0.5 * sin sum  -- kept as separate factors: (.. * dyc) * 0.5 * (sin + sin)
-        Real d, ss;
-        bool edge;
-      };
-      auto UFm = [&](int ii, int jj) {
-        const unsigned q = IX(ii, jj), qm = IX(ii, jj - 1);
-        Face m;
-        m.edge = (S && jj == 1) || (N && jj == npy);
-        m.cs = (g.cos_sg4 + m2)[qm] + (g.cos_sg2 + m2)[q];
-        m.d = (g.dyc + m2)[q];
-        m.ss = (g.sin_sg4 + m2)[qm] + (g.sin_sg2 + m2)[q];
-        m.f = (Real)0;
-        return m;
-      };
-      auto VFm = [&](int ii, int jj) {
-        const unsigned q = IX(ii, jj), qm = IX(ii - 1, jj);
-        Face m;
-        m.edge = (W && ii == 1) || (E && ii == npx);
-        m.cs = (g.cos_sg3 + m2)[qm] + (g.cos_sg1 + m2)[q];
-        m.d = (g.dxc + m2)[q];
-        m.ss = (g.sin_sg3 + m2)[qm] + (g.sin_sg1 + m2)[q];
-        m.f = (Real)0;
-        return m;
-      };
-      const Face mu0 = UFm(i - 1, j), mu1 = UFm(i, j), mv0 = VFm(i, j - 1), mv1 = VFm(i, j);
-      const bool cSW = W && S && i == 1 && j == 1, cSE = E && S && i == npx && j == 1, cNE = E && N && i == npx && j == npy, cNW = W && N && i == 1 && j == npy;
-      Face mvc = mv0;
-      if (cSW) mvc = VFm(1, 0);
-      if (cSE) mvc = VFm(npx, 0);
-      if (cNE) mvc = VFm(npx, npy);
-      if (cNW) mvc = VFm(1, npy);
-      const Real rac = (g.rarea_c + m2)[IX(i, j)];
-#pragma unroll 1
-      for (int kk = 0; kk < KC; ++kk) {
-        const int k = KC * kp + kk;
-        if (k > nz1) break;
-        const long b = t * g.st + k * g.sk;
-        auto UF = [&](int ii, int jj, const Face &m) -> Real {
-          const unsigned q = IX(ii, jj), qm = IX(ii, jj - 1);
-          if (m.edge) return (u + b)[q] * m.d * (Real)0.5 * m.ss;
-          return ((u + b)[q] - (Real)0.25 * ((va + b)[qm] + (va + b)[q]) * m.cs) * m.d * (Real)0.5 * m.ss;
-        };
-        auto VF = [&](int ii, int jj, const Face &m) -> Real {
-          const unsigned q = IX(ii, jj), qm = IX(ii - 1, jj);
-          if (m.edge) return (v + b)[q] * m.d * (Real)0.5 * m.ss;
-          return ((v + b)[q] - (Real)0.25 * ((ua + b)[qm] + (ua + b)[q]) * m.cs) * m.d * (Real)0.5 * m.ss;
-        };
-        Real dv = VF(i, j - 1, mv0) - VF(i, j, mv1) + UF(i - 1, j, mu0) - UF(i, j, mu1);
-        if (cSW) dv -= VF(1, 0, mvc);
-        if (cSE) dv -= VF(npx, 0, mvc);
-        if (cNE) dv += VF(npx, npy, mvc);
-        if (cNW) dv += VF(1, npy, mvc);
-        (divgd + b)[IX(i, j)] = rac * dv;
-      }
+// (C) divergence on corners (nord > 0).  Two levels per thread: the ten metric terms of a corner are read once and
+// used for both levels (they are 2/3 of this kernel's bytes).
+static void csw_stage_c(fv3_ctx *c, fv3_stream_t s, const CswPlan &pl, const CswFields &f) {
+  const Geo g = c->g;
+  const CswGeom gm = csw_geom(g.nx, g.ny, g.npx, g.npy, pl.form, CSW_ST_C);
+  const int KC = pl.KC, nz1 = g.nz - 1;
+  Real *u = f.u, *v = f.v, *ua = f.ua, *va = f.va, *divgd = f.divgd;
+  csw_launch(c, s, pl, CSW_ST_C, [=] FV3_HD(int t, int kp, int i, int j) {
+    const int fl = g.flags[t];
+    if (csw_interior_owns(gm, CSW_ST_C, fl, i, j)) return;  // the corners whose 2 x 2 block of ua / va the marching kernel holds are done there
+    const long m2 = t * g.st2;
+    const bool W = fl & FV3_W, E = fl & FV3_E, S = fl & FV3_S, N = fl & FV3_N;
+    const int npx = g.npx, npy = g.npy;
+    // metric factors of the four faces around the corner (exactly the sub-expressions of the one-level form)
+    struct Face {
+      Real cs, f;  // cos sum, dyc * 0.5 * sin sum  -- kept as separate factors: (.. * dyc) * 0.5 * (sin + sin)
+      Real d, ss;
+      bool edge;
     };
-    if (march) {  // the four windows along the sub-domain boundary
-      const int e0 = g.nx - 3;
-      launch_frame(c, s, Frame{{Box{1, 5, 1, g.ny + 1, 0, npair - 1}, Box{e0, e0 + 4, 1, g.ny + 1, 0, 0}, Box{6, g.nx - 4, 1, 5, 0, 0}, Box{6, g.nx - 4, g.ny - 3, g.ny + 1, 0, 0}}}, stage_c);
-    } else {
-      launch3(c, s, Box{1, g.nx + 1, 1, g.ny + 1, 0, npair - 1}, stage_c);
+    auto UFm = [&](int ii, int jj) {
+      const unsigned q = IX(ii, jj), qm = IX(ii, jj - 1);
+      Face m;
+      m.edge = (S && jj == 1) || (N && jj == npy);
+      m.cs = (g.cos_sg4 + m2)[qm] + (g.cos_sg2 + m2)[q];
+      m.d = (g.dyc + m2)[q];
+      m.ss = (g.sin_sg4 + m2)[qm] + (g.sin_sg2 + m2)[q];
+      m.f = (Real)0;
+      return m;
+    };
+    auto VFm = [&](int ii, int jj) {
+      const unsigned q = IX(ii, jj), qm = IX(ii - 1, jj);
+      Face m;
+      m.edge = (W && ii == 1) || (E && ii == npx);
+      m.cs = (g.cos_sg3 + m2)[qm] + (g.cos_sg1 + m2)[q];
+      m.d = (g.dxc + m2)[q];
+      m.ss = (g.sin_sg3 + m2)[qm] + (g.sin_sg1 + m2)[q];
+      m.f = (Real)0;
+      return m;
+    };
+    const Face mu0 = UFm(i - 1, j), mu1 = UFm(i, j), mv0 = VFm(i, j - 1), mv1 = VFm(i, j);
+    const bool cSW = W && S && i == 1 && j == 1, cSE = E && S && i == npx && j == 1, cNE = E && N && i == npx && j == npy, cNW = W && N && i == 1 && j == npy;
+    Face mvc = mv0;
+    if (cSW) mvc = VFm(1, 0);
+    if (cSE) mvc = VFm(npx, 0);
+    if (cNE) mvc = VFm(npx, npy);
+    if (cNW) mvc = VFm(1, npy);
+    const Real rac = (g.rarea_c + m2)[IX(i, j)];
+#pragma unroll 1
+    for (int kk = 0; kk < KC; ++kk) {
+      const int k = KC * kp + kk;
+      if (k > nz1) break;
+      const long b = t * g.st + k * g.sk;
+      auto UF = [&](int ii, int jj, const Face &m) -> Real {
+        const unsigned q = IX(ii, jj), qm = IX(ii, jj - 1);
+        if (m.edge) return (u + b)[q] * m.d * (Real)0.5 * m.ss;
+        return ((u + b)[q] - (Real)0.25 * ((va + b)[qm] + (va + b)[q]) * m.cs) * m.d * (Real)0.5 * m.ss;
+      };
+      auto VF = [&](int ii, int jj, const Face &m) -> Real {
+        const unsigned q = IX(ii, jj), qm = IX(ii - 1, jj);
+        if (m.edge) return (v + b)[q] * m.d * (Real)0.5 * m.ss;
+        return ((v + b)[q] - (Real)0.25 * ((ua + b)[qm] + (ua + b)[q]) * m.cs) * m.d * (Real)0.5 * m.ss;
+      };
+      Real dv = VF(i, j - 1, mv0) - VF(i, j, mv1) + UF(i - 1, j, mu0) - UF(i, j, mu1);
+      if (cSW) dv -= VF(1, 0, mvc);
+      if (cSE) dv -= VF(npx, 0, mvc);
+      if (cNE) dv += VF(npx, npy, mvc);
+      if (cNW) dv += VF(1, npy, mvc);
+      (divgd + b)[IX(i, j)] = rac * dv;
     }
-  }
+  });
+}
 
-  // (D) upwind transport (delpc, ptc, wc), kinetic energy, absolute vorticity
-  auto stage_d = [=] FV3_HD(int t, int kp, int i_, int j_) {
+// (D) upwind transport (delpc, ptc, wc), kinetic energy, absolute vorticity
+static void csw_stage_d(fv3_ctx *c, fv3_stream_t s, const CswPlan &pl, const CswFields &f) {
+  const Geo g = c->g;
+  const CswGeom gm = csw_geom(g.nx, g.ny, g.npx, g.npy, pl.form, CSW_ST_D);
+  const int KC = pl.KC, nz1 = g.nz - 1;
+  Real *delp = f.delp, *pt = f.pt, *u = f.u, *v = f.v, *w = f.w, *uc = f.uc, *vc = f.vc, *ua = f.ua, *va = f.va, *ut = f.ut, *vt = f.vt;
+  Real *omga = f.omga, *delpc = f.delpc, *ptc = f.ptc, *ke = f.ke, *vort = f.vort;
+  const Real dt2 = f.dt2;
+  csw_launch(c, s, pl, CSW_ST_D, [=] FV3_HD(int t, int kp, int i_, int j_) {
     const int fl = g.flags[t];
     // (fused form: the cells of RD and the corners of VR are done by the marching kernel -- see csw_fused_stream)
     bool do_cell = true, do_vort = true;
-    if (fused) {
-      const CswRect rc = b_rect(fl);
-      do_cell = !(i_ >= rc.i_lo && i_ <= rc.i_hi - 1 && j_ >= rc.j_lo && j_ <= rc.j_hi - 1);
-      do_vort = !(i_ >= rc.i_lo + 1 && i_ <= rc.i_hi && j_ >= rc.j_lo + 1 && j_ <= rc.j_hi);
-      if (!do_cell && !do_vort) return;
+    if (gm.framed) {
+      const CswRect rc = gm.rect(fl);
+      do_cell = !csw_RD(rc, i_, j_);
+      do_vort = !csw_VR(rc, i_, j_);
+      if (!do_cell && !do_vort) return;  // (csw_interior_owns)
     }
     const long m2 = t * g.st2;
     const bool W = fl & FV3_W, E = fl & FV3_E, S = fl & FV3_S, N = fl & FV3_N;
@@ -1154,31 +1171,19 @@ extern "C" int fv3_c_sw(fv3_ctx *c, const fv3_field *delp_, const fv3_field *pt_
       (vort + b)[p] = m_fc + m_rac * vo;
     }
     }
-  };
-  // Round 6, FV3_CSW_DEFER=1 (measured, NOT the default: R6-11): inside the sequencer the eight window launches of stages D and E (1.15 ms of small launches behind
-  // the march) go to the auxiliary stream and the operator returns without waiting for them: update_dz_c, which follows, reads ut / vt / zh only, and
-  // riem_solver_c -- the first reader of the windows' delpc / ptc / wc -- is where the sequencer joins (fv3_csw_join).  Same values; c_sw shrinks by 1.1 ms and
-  // update_dz_c, bandwidth-bound beside the windows, grows by 0.85: four same-box pairs gave -0.7 / -0.0 / +0.6 / +0.1 ms per sub-step.  Events 6 = fork, 7 = join.
-  static const bool defer_on = fv3_sw(FV3SW_CSW_DEFER);
-  fv3_stream_t sd_ = (fused && defer_on && c->seq.csw_defer) ? fv3_aux(c, s) : s;
-  if (sd_ != s) {
-    fv3_signal(c, s, EV_CSW_LATE_FORK);
-    fv3_wait(c, sd_, EV_CSW_LATE_FORK);
-  }
-  if (fused) {  // the four windows along the sub-domain boundary
-    const int e0 = g.nx - 4;
-    launch_frame(c, sd_, Frame{{Box{0, 6, 0, g.ny + 1, 0, nkc - 1}, Box{e0, e0 + 5, 0, g.ny + 1, 0, 0}, Box{7, g.nx - 5, 0, 6, 0, 0}, Box{7, g.nx - 5, g.ny - 4, g.ny + 1, 0, 0}}}, stage_d);
-  } else {
-    launch3(c, s, Box{0, g.nx + 1, 0, g.ny + 1, 0, nkc - 1}, stage_d);
-  }
+  });
+}
 
-  // (E) time-centred C-grid winds (two levels per thread: the six metric terms are read once)
-  auto stage_e = [=] FV3_HD(int t, int kp, int i, int j) {
+// (E) time-centred C-grid winds (two levels per thread: the six metric terms are read once)
+static void csw_stage_e(fv3_ctx *c, fv3_stream_t s, const CswPlan &pl, const CswFields &f) {
+  const Geo g = c->g;
+  const CswGeom gm = csw_geom(g.nx, g.ny, g.npx, g.npy, pl.form, CSW_ST_E);
+  const int KC = pl.KC, nz1 = g.nz - 1;
+  Real *u = f.u, *v = f.v, *uc = f.uc, *vc = f.vc, *ke = f.ke, *vort = f.vort;
+  const Real dt2 = f.dt2;
+  csw_launch(c, s, pl, CSW_ST_E, [=] FV3_HD(int t, int kp, int i, int j) {
     const int fl = g.flags[t];
-    if (fused) {  // the cells of RE are done by the marching kernel
-      const CswRect rc = b_rect(fl);
-      if (i >= rc.i_lo + 1 && i <= rc.i_hi - 1 && j >= rc.j_lo + 1 && j <= rc.j_hi - 1) return;
-    }
+    if (csw_interior_owns(gm, CSW_ST_E, fl, i, j)) return;  // the cells of RE are done by the marching kernel
     const long m2 = t * g.st2;
     const bool W = fl & FV3_W, E = fl & FV3_E, S = fl & FV3_S, N = fl & FV3_N;
     const int npx = g.npx, npy = g.npy;
@@ -1204,18 +1209,48 @@ extern "C" int fv3_c_sw(fv3_ctx *c, const fv3_field *delp_, const fv3_field *pt_
         (vc + b)[p] = vcv - fx1 * fxv + rdyc * ((ke + b)[IX(i, j - 1)] - (ke + b)[p]);
       }
     }
-  };
-  {
-    const int nke = (nz1 + KC) / KC - 1;
-    if (fused) {
-      const int e0 = g.nx - 4;
-      launch_frame(c, sd_, Frame{{Box{1, 6, 1, g.ny + 1, 0, nke}, Box{e0, e0 + 5, 1, g.ny + 1, 0, 0}, Box{7, g.nx - 5, 1, 6, 0, 0}, Box{7, g.nx - 5, g.ny - 4, g.ny + 1, 0, 0}}}, stage_e);
-    } else {
-      launch3(c, s, Box{1, g.nx + 1, 1, g.ny + 1, 0, nke}, stage_e);
-    }
+  });
+}
+
+extern "C" int fv3_c_sw(fv3_ctx *c, const fv3_field *delp_, const fv3_field *pt_, const fv3_field *u_, const fv3_field *v_, const fv3_field *w_,
+                        const fv3_field *uc_, const fv3_field *vc_, const fv3_field *ua_, const fv3_field *va_, const fv3_field *ut_, const fv3_field *vt_,
+                        const fv3_field *divgd_, const fv3_field *omga_, const fv3_field *delpc_, const fv3_field *ptc_, double dt2d, void *stream) {
+  if (!c) return FV3_ERR_ARG;
+  FV3_FIELD(delp, delp_) FV3_FIELD(pt, pt_) FV3_FIELD(u, u_) FV3_FIELD(v, v_) FV3_FIELD(w, w_) FV3_FIELD(uc, uc_) FV3_FIELD(vc, vc_)
+  FV3_FIELD(ua, ua_) FV3_FIELD(va, va_) FV3_FIELD(ut, ut_) FV3_FIELD(vt, vt_) FV3_FIELD(divgd, divgd_) FV3_FIELD(omga, omga_)
+  FV3_FIELD(delpc, delpc_) FV3_FIELD(ptc, ptc_)
+  const fv3_stream_t s = (fv3_stream_t)stream;
+  const CswFields f{delp, pt, u, v, w, uc, vc, ua, va, ut, vt, divgd, omga, delpc, ptc, c->scratch[SC_A], c->scratch[SC_B], (Real)dt2d};
+  const CswPlan pl = csw_plan(c, s);
+  if (pl.report) fprintf(stderr, "[c_sw] %s\n", pl.report);
+  // stages A and B: their windows (pl.s_ab) beside the interior kernel of the form (s)
+  if (pl.s_ab != s) {
+    fv3_signal(c, s, EV_FORK);
+    fv3_wait(c, pl.s_ab, EV_FORK);
   }
-  if (sd_ != s) {
-    fv3_signal(c, sd_, EV_CSW_LATE_JOIN);
+  csw_stage_a(c, pl.s_ab, pl, f);
+  if (pl.form == CSW_FUSED)
+    csw_fused_stream(c, s, pl, f);
+  else if (pl.form == CSW_ABC)
+    csw_abc_stream(c, s, pl, f);
+  else if (pl.form == CSW_TWO_ROW)
+    csw_two_row_b(c, s, pl, f);
+  csw_stage_b(c, pl.s_ab, pl, f);
+  if (pl.s_ab != s) {
+    fv3_signal(c, pl.s_ab, EV_WIN_JOIN);
+    fv3_wait(c, s, EV_WIN_JOIN);
+  }
+  csw_uava_corners(c, s, pl, f);
+  if (pl.do_div) csw_stage_c(c, s, pl, f);
+  // stages D and E (pl.s_de: with defer the operator returns while they run)
+  if (pl.defer) {
+    fv3_signal(c, s, EV_CSW_LATE_FORK);
+    fv3_wait(c, pl.s_de, EV_CSW_LATE_FORK);
+  }
+  csw_stage_d(c, pl.s_de, pl, f);
+  csw_stage_e(c, pl.s_de, pl, f);
+  if (pl.defer) {
+    fv3_signal(c, pl.s_de, EV_CSW_LATE_JOIN);
     c->csw_pending = true;  // (the sequencer joins: fv3_csw_join)
   }
   return fv3_post(c, s, "c_sw");

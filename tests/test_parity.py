@@ -212,23 +212,25 @@ def test_riem_solver3_and_column_ops(backend):
     assert_close("pe ring", Q["pe"].numpy(0)[R1], x["pe"][R1], 1e-14, 1e-14)
 
 
-def test_c_sw_forms_are_bitwise_equal(backend, monkeypatch):
+@pytest.mark.parametrize("n, layout, ranks", [(48, (2, 2), (0, 5, 10, 15)), (16, (1, 1), (0,))], ids=["c48_2x2", "c16_1x1"])
+def test_c_sw_forms_are_bitwise_equal(backend, monkeypatch, n, layout, ranks):
     """The four forms of c_sw (the whole interior as one marching kernel / stages A - C as a marching kernel + stage kernels /
     two-row stage kernel + stage kernels / generic stage kernels everywhere) evaluate the same expressions in the same order:
-    every output is bitwise equal."""
-    nz, outs = 3, {}
+    every output is bitwise equal.  C16 1x1: nx = 16 is the smallest size with an interior kernel, the one sub-domain has all four
+    tile edges, the interior rectangle is 7 x 7 and the W and E windows nearly meet."""
+    nz, outs, nr = 3, {}, len(ranks)
     for form, env in (("march", {}), ("abc", {"FV3_CSW_MARCH": "abc"}), ("two_row", {"FV3_CSW_MARCH": "0"}), ("generic", {"FV3_CSW_B_GENERIC": "1"})):
         for k in ("FV3_CSW_MARCH", "FV3_CSW_B_GENERIC"):
             monkeypatch.delenv(k, raising=False)
         for k, v_ in env.items():
             monkeypatch.setenv(k, v_)
         monkeypatch.setenv("FV3_SEG", "8")
-        cs = Case(48, (2, 2), (0, 5, 10, 15), nz=nz, backend=backend)
+        cs = Case(n, layout, ranks, nz=nz, backend=backend)
         names = ("delp", "pt", "u", "v", "w", "uc", "vc", "ua", "va", "omga")
-        Q = {n: cs.q([s[n] for s in cs.states]) for n in names}
+        Q = {k: cs.q([s[k] for s in cs.states]) for k in names}
         extra = [cs.q() for _ in range(5)]
-        cs.sf.call("c_sw", *[Q[n].fref for n in names[:9]], extra[0].fref, extra[1].fref, extra[2].fref, Q["omga"].fref, extra[3].fref, extra[4].fref, 56.25)
-        outs[form] = [Q[n].numpy(r).copy() for n in ("uc", "vc", "ua", "va", "omga") for r in range(4)] + [e.numpy(r).copy() for e in extra for r in range(4)]
+        cs.sf.call("c_sw", *[Q[k].fref for k in names[:9]], extra[0].fref, extra[1].fref, extra[2].fref, Q["omga"].fref, extra[3].fref, extra[4].fref, 56.25)
+        outs[form] = [Q[k].numpy(r).copy() for k in ("uc", "vc", "ua", "va", "omga") for r in range(nr)] + [e.numpy(r).copy() for e in extra for r in range(nr)]
     for form in ("abc", "two_row", "generic"):
         for a, b in zip(outs["march"], outs[form]):
             assert np.array_equal(a, b), form
