@@ -19,7 +19,17 @@ mid-points (second order), and on a face that lies on a tile edge the C-grid com
   pin 5a nh_p_grad, p_grad_c  no force on an isentropic atmosphere at rest over terrain                    (resting_state, check_no_force)
   pin 5b remap        layer means linear in pressure stay linear in pressure                         (linear_columns, linear_winds)
 
-``python tests/analytic_case.py --record`` measures the numpy oracle's error on the same inputs and writes tests/golden/analytic_pins.json;
+and of tests/test_analytic_dynamics.py, on the same rotation with every damping term of d_sw off (DSW_OFF) at a Courant number of 0.1 x 24 / n (dyn_dt):
+
+  pin 6  d_sw         scalars at their departure points, mass fluxes and Courant numbers accumulated     (DswCase.scalar_errors)
+  pin 7  d_sw         the wind tendency against -(zeta + f) k x V - grad K by class of faces, and the
+                      closed-form kinetic-energy excess of tile-edge corners, 0.5 cot(alpha) Vn Vt       (DswCase.wind_errors, face_classes, edge_ke_excess)
+  pin 8  riem_solver3, riem_solver_c   columns held at and relaxed to the hydrostatic thickness of the gas law  (Columns, riem_figures, check_balanced, check_relaxed)
+  pin 9  update_dz_d  interface heights at their departure points, no surface velocity over flat ground    (HeightCase)
+
+Edge lengths (pin 7) are great-circle distances of the corners (arc), never dx / dy.
+
+``python tests/analytic_case.py --record`` (``--record dynamics``: pins 6 - 9 alone, the other entries kept) measures the numpy oracle's error on the same inputs and writes tests/golden/analytic_pins.json;
 the tests hold the library to 1.5 x those figures and to the second-order ratio between C24 and C48 (check_convergence).
 """
 import json
@@ -522,6 +532,475 @@ def check_linear(label, got, want, profile_range, bound=1e-13):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
+# pins 6 and 7: d_sw on solid-body rotation with every damping term off (tests/test_analytic_dynamics.py)
+# ---------------------------------------------------------------------------------------------------------------------------
+DYN_NZ = 3
+DSW_OFF = dict(nord=0, d2_bg=0.0, d2_bg_k1=0.0, d2_bg_k2=0.0, d4_bg=0.0, dddmp=0.0, d_con=0.0, vtdm4=0.0, ke_bg=0.0, do_vort_damp=False, n_sponge=-1)
+D_SW_ORDER = ("delpc", "delp", "pt", "u", "v", "w", "uc", "vc", "ua", "va", "divgd", "mfxd", "mfyd", "cxd", "cyd", "crx", "cry", "xfx", "yfx", "q_con", "zh", "heat_source", "diss_est")
+D_SW_INPUTS = ("delp", "pt", "u", "v", "w", "uc", "vc", "mfxd", "mfyd", "cxd", "cyd", "q_con")
+SCALARS = ("delp", "pt", "w", "q_con")
+K_PT, K_W, K_QC = np.array([-0.9, 1.6, 0.8]), np.array([2.2, 0.6, -1.1]), np.array([0.5, -1.9, 1.4])
+Z_AXIS = (0.0, 0.0, 1.0)
+SECOND, INTERIOR = 2, 3  # face classes of pin 7 after 0 and 1
+CLASS_KEYS = {0: "class0", 1: "class1", SECOND: "second_line", INTERIOR: "class2"}
+
+
+def dyn_dt(n, flow):
+    """Courant number 0.1 at C24 and falling as 1 / n: dt falls as 1 / n^2, so that the error of one call measures the scheme's truncation
+    and not the time step's"""
+    return 0.1 * (24.0 / n) * 0.7 * flow.a * (np.pi / 2.0) / n / flow.u0
+
+
+def _wave(p, kvec, phase):
+    return np.sin(np.sum(p * kvec, -1) + phase) + 0.5 * np.cos(2.0 * p[..., 1] + p[..., 2] - phase)
+
+
+# the scalars d_sw transports, as functions of position [..., 3] -> [..., nz]; SCALAR_SCALE is the amplitude the errors are quoted against
+SCALAR_SCALE = {"delp": 1000.0, "pt": 20.0, "w": 1.0, "q_con": 0.01}
+
+
+def scalar_field(name, p, nz=DYN_NZ):
+    if name == "delp":
+        return levels_last(1000.0 * (2.5 + smooth(p)), nz)
+    kvec, base, amp = {"pt": (K_PT, 300.0, 20.0), "w": (K_W, 2.5, 1.0), "q_con": (K_QC, 0.025, 0.01)}[name]
+    return np.stack([base + amp * _wave(p, kvec, 0.3 + 0.7 * k) for k in range(nz)], -1)
+
+
+def levels_last(a, nz):
+    return np.repeat(np.asarray(a)[..., None], nz, -1)
+
+
+def arc(a, b):
+    """great-circle angle between unit vectors"""
+    return np.arctan2(np.linalg.norm(np.cross(a, b), axis=-1), np.sum(a * b, -1))
+
+
+def face_classes(G):
+    """(classes of the u faces [nx, ny + 1], of the v faces [nx + 1, ny]) by the distance in lines from the nearest cube-tile edge: 0 on the edge;
+    1 the line next to it in the cross direction (u in cell columns 1 and nx, v in cell rows 1 and ny: faces with one end on the edge); SECOND the line
+    after either (u in corner rows 2 and ny, cell columns 2 and nx - 1); INTERIOR two or more lines from every tile edge -- the edges of a sub-domain
+    inside a tile included"""
+    g = G.g
+    cu, cv = np.full((g.nx, g.ny + 1), INTERIOR), np.full((g.nx + 1, g.ny), INTERIOR)
+    cross, along = (g.west_edge, g.east_edge), (g.south_edge, g.north_edge)
+    for value, first in ((SECOND, 1), (1, 0)):  # the cross direction of u is x, of v (seen transposed) y
+        for c, (lo, hi) in ((cu, cross), (cv.T, along)):
+            if lo:
+                c[first, :] = value
+            if hi:
+                c[-1 - first, :] = value
+    for c, (lo, hi) in ((cu, along), (cv.T, cross)):
+        if lo:
+            c[:, 1] = np.minimum(c[:, 1], SECOND)
+            c[:, 0] = 0
+        if hi:
+            c[:, -2] = np.minimum(c[:, -2], SECOND)
+            c[:, -1] = 0
+    return cu, cv
+
+
+def edge_ke_excess(G, flow):
+    """0.5 cot(alpha) Vn Vt on the compute corners [nx + 1, ny + 1] that lie on a cube-tile edge (0 elsewhere and on the cube corners): what d_sw's
+    corner kinetic energy holds above 0.5 |V|^2 there.  With t the edge's tangent, n its normal and e the direction of the grid line that crosses the
+    edge on the upstream side (all three from corner positions): Vn = V . n, Vt = V . t, cot(alpha) = (e . t) / (e . n)."""
+    P, g = G.P, G.g
+    ex = np.zeros((g.nx + 1, g.ny + 1))
+
+    def term(p, along_m, along_p, cross_m, cross_p):
+        t = _tangent(along_p - along_m, p)
+        e_m, e_p = _tangent(p - cross_m, p), _tangent(cross_p - p, p)
+        n = _unit(e_p - np.sum(e_p * t, -1, keepdims=True) * t)
+        V = flow.wind(p)
+        vn, vt = np.sum(V * n, -1), np.sum(V * t, -1)
+        e = np.where((vn > 0.0)[..., None], e_m, e_p)
+        return 0.5 * np.sum(e * t, -1) / np.sum(e * n, -1) * vn * vt
+
+    J = slice(NH + 1, NH + g.ny)  # without the cube corners
+    for flag, i, I in ((g.west_edge, 0, NH), (g.east_edge, -1, NH + g.nx)):
+        if flag:
+            ex[i, 1:-1] = term(P[I, J], P[I, NH : NH + g.ny - 1], P[I, NH + 2 : NH + g.ny + 1], P[I - 1, J], P[I + 1, J])
+    Ii = slice(NH + 1, NH + g.nx)
+    for flag, j, Jj in ((g.south_edge, 0, NH), (g.north_edge, -1, NH + g.ny)):
+        if flag:
+            ex[1:-1, j] = term(P[Ii, Jj], P[NH : NH + g.nx - 1, Jj], P[NH + 2 : NH + g.nx + 1, Jj], P[Ii, Jj - 1], P[Ii, Jj + 1])
+    if not (g.west_edge or g.east_edge or g.south_edge or g.north_edge):
+        return ex
+    # a sub-domain that holds part of an edge: the end corners of that part are ordinary edge corners, not cube corners
+    for flag, i, I in ((g.west_edge, 0, NH), (g.east_edge, -1, NH + g.nx)):
+        if flag:
+            for on_tile_corner, j, Jj in ((g.south_edge, 0, NH), (g.north_edge, -1, NH + g.ny)):
+                if not on_tile_corner:
+                    ex[i, j] = term(P[I, Jj], P[I, Jj - 1], P[I, Jj + 1], P[I - 1, Jj], P[I + 1, Jj])
+    for flag, j, Jj in ((g.south_edge, 0, NH), (g.north_edge, -1, NH + g.ny)):
+        if flag:
+            for on_tile_corner, i, I in ((g.west_edge, 0, NH), (g.east_edge, -1, NH + g.nx)):
+                if not on_tile_corner:
+                    ex[i, j] = term(P[I, Jj], P[I - 1, Jj], P[I + 1, Jj], P[I, Jj - 1], P[I, Jj + 1])
+    return ex
+
+
+class DswCase:
+    """d_sw on solid-body rotation, per rank r: ins[r] the inputs [i, j, nz] over the whole storage (u, v, uc, vc analytic; delp, pt, w, q_con
+    smooth positive functions of position; mfxd, mfyd, cxd, cyd pre-filled with a smooth non-zero field), and the closed-form answers."""
+
+    def __init__(self, n, grids, a, omega_earth, axis=AXIS, nz=DYN_NZ):
+        self.n, self.grids, self.nz, self.rot = n, grids, nz, float(omega_earth)
+        self.flow = Flow(a, axis)
+        self.dt = dyn_dt(n, self.flow)
+        self.G = [Geometry(g) for g in grids]
+        self.ins = []
+        for G in self.G:
+            u, v = self.flow.d_grid(G)
+            uc, vc = self.flow.c_grid(G)
+            sx, sy = self.flow.swept(G, self.dt)
+            x = {"u": levels(u, nz), "v": levels(v, nz), "uc": levels(uc, nz), "vc": levels(vc, nz)}
+            x.update({k: scalar_field(k, G.C, nz) for k in SCALARS})
+            top = 1000.0 * max(np.abs(sx[G.X]).max(), np.abs(sy[G.Y]).max())
+            x["mfxd"], x["mfyd"] = levels(top * (2.0 + smooth(G.mx)), nz), levels(top * (2.0 + smooth(G.my)), nz)
+            x["cxd"], x["cyd"] = levels(0.05 * (2.0 + smooth(G.mx)), nz), levels(0.05 * (2.0 + smooth(G.my)), nz)
+            self.ins.append(x)
+
+    def tendency(self, p):
+        """T(p) = -(zeta + f) p x V - grad K of the rotation: zeta = 2 omega s, f = 2 OMEGA p_z, K = U0^2 (1 - s^2) / 2, s = p . axis"""
+        fl = self.flow
+        s = np.sum(p * fl.axis, -1, keepdims=True)
+        return -(2.0 * fl.omega * s + 2.0 * self.rot * p[..., 2:3]) * np.cross(p, fl.wind(p)) + (fl.u0**2 / fl.a) * s * (fl.axis - s * p)
+
+    def scalar_errors(self, outs, way=1.0):
+        """max |got - exact| / SCALAR_SCALE over the cells of every rank, per transported scalar; mfx / mfy and cx / cy relative to the largest exact
+        value; max |heat_source|, |diss_est|.  way = -1: against the solution turned the wrong way (the control)"""
+        fl, dt, nz = self.flow, self.dt, self.nz
+        err = dict.fromkeys(SCALARS + ("mfx", "mfy", "cx", "cy", "heat", "diss"), 0.0)
+        top = dict.fromkeys(("mfx", "mfy", "cx", "cy"), 0.0)
+        for g, G, x, o in zip(self.grids, self.G, self.ins, outs):
+            o = {k: np.asarray(v, dtype=np.float64)[:, :, :nz] for k, v in o.items() if v is not None}
+            back = fl.rotate_back(G.C[G.cells], way * dt)
+            for k in SCALARS:
+                require(np.all(np.isfinite(o[k][G.cells])), f"{k}: non-finite")
+                err[k] = max(err[k], float(np.abs(o[k][G.cells] - scalar_field(k, back, nz)).max()) / SCALAR_SCALE[k])
+            sx, sy = fl.swept(G, dt)
+            for k, name, m, s, F in (("mfx", "mfxd", G.mx, sx, G.X), ("mfy", "mfyd", G.my, sy, G.Y)):
+                want = scalar_field("delp", fl.rotate_back(m[F], way * 0.5 * dt), nz) * s[F][..., None]
+                err[k], top[k] = max(err[k], float(np.abs((o[name] - x[name])[F] - want).max())), max(top[k], float(np.abs(want).max()))
+            dcx, dcy = o["cxd"] - x["cxd"], o["cyd"] - x["cyd"]
+            ux, uy = upwind_area(g, dcx, dcy)
+            for k, d, up, s, F in (("cx", dcx, ux, sx, G.X), ("cy", dcy, uy, sy, G.Y)):
+                err[k], top[k] = max(err[k], float(np.abs((d * up)[F] - s[F][..., None]).max())), max(top[k], float(np.abs(s[F]).max()))
+            err["heat"] = max(err["heat"], float(np.abs(o["heat_source"][G.cells]).max()))
+            err["diss"] = max(err["diss"], float(np.abs(o["diss_est"][G.cells]).max()))
+        for k in top:
+            err[k] /= top[k]
+        return err
+
+    def wind_residuals(self, outs):
+        """per rank: (classes, tendency residual, closed-form edge term) of the u faces and of the v faces, with the largest exact tendency.  The
+        tendency is (u_out / L - u_in) / dt, L the great-circle length of the face's edge (d_sw returns u dx)."""
+        fl, dt, nz = self.flow, self.dt, self.nz
+        res, top = [], 0.0
+        for G, x, o in zip(self.G, self.ins, outs):
+            P = G.P
+            Lu, Lv = fl.a * _grow(arc(P[:-1, :], P[1:, :]), P.shape[:2]), fl.a * _grow(arc(P[:, :-1], P[:, 1:]), P.shape[:2])
+            ex = edge_ke_excess(G, fl)
+            cu, cv = face_classes(G)
+            tu = (np.asarray(o["u"], dtype=np.float64)[:, :, :nz][G.Y] / Lu[G.Y][..., None] - x["u"][G.Y]) / dt
+            tv = (np.asarray(o["v"], dtype=np.float64)[:, :, :nz][G.X] / Lv[G.X][..., None] - x["v"][G.X]) / dt
+            require(np.all(np.isfinite(tu)) and np.all(np.isfinite(tv)), "non-finite wind")
+            wu, wv = np.sum(self.tendency(G.my[G.Y]) * G.tx[G.Y], -1), np.sum(self.tendency(G.mx[G.X]) * G.ty[G.X], -1)
+            top = max(top, float(np.abs(wu).max()), float(np.abs(wv).max()))
+            res.append(((cu, tu - wu[..., None], ((ex[:-1, :] - ex[1:, :]) / Lu[G.Y])[..., None]), (cv, tv - wv[..., None], ((ex[:, :-1] - ex[:, 1:]) / Lv[G.X])[..., None])))
+        return res, top
+
+    def wind_errors(self, outs, only=None):
+        """max |tendency - exact| / max |exact| per class of faces (face_classes): {"class0", "class1", "second_line", "class2" (two or more lines
+        from every tile edge), and "class0_less_edge_term", "class1_less_edge_term": with the closed-form edge term taken off; "class0_inner": class 0 without the faces
+        that end on a cube corner, where d_sw's corner kinetic energy is another formula}.  only(rank index, "u" | "v", G) -> mask of the faces to look at (default: all)"""
+        res, top = self.wind_residuals(outs)
+        err = dict.fromkeys(list(CLASS_KEYS.values()) + ["class0_less_edge_term", "class1_less_edge_term", "class0_inner", "class0_inner_less_edge_term"], 0.0)
+        for r, pair in enumerate(res):
+            for which, (cls, d, edge) in zip("uv", pair):
+                keep = np.ones(cls.shape, bool) if only is None else only(r, which, self.G[r])
+                for c, key in CLASS_KEYS.items():
+                    m = (cls == c) & keep
+                    if m.any():
+                        err[key] = max(err[key], float(np.abs(d[m]).max()))
+                        if c in (0, 1):
+                            err[key + "_less_edge_term"] = max(err[key + "_less_edge_term"], float(np.abs((d - edge)[m]).max()))
+                if which == "v":
+                    cls, d, edge, keep = cls.T, d.transpose(1, 0, 2), edge.transpose(1, 0, 2), keep.T
+                m = ((cls == 0) & keep)[1:-1]  # on the edge, without the two faces that end on a cube corner
+                if m.any():
+                    err["class0_inner"] = max(err["class0_inner"], float(np.abs(d[1:-1][m]).max()))
+                    err["class0_inner_less_edge_term"] = max(err["class0_inner_less_edge_term"], float(np.abs((d - edge)[1:-1][m]).max()))
+        return {k: v / top for k, v in err.items()}
+
+
+def tile0_east(r, which, G):
+    """the faces of pin 7's z-axis control: the u faces of the cell column next to the east edge"""
+    m = np.zeros((G.nx, G.ny + 1) if which == "u" else (G.nx + 1, G.ny), bool)
+    if which == "u" and G.g.east_edge:
+        m[-1, :] = True
+    return m
+
+
+def dyn_config(n, layout, nz=DYN_NZ, **kw):
+    from pace_amd.config import AcousticDynamicsConfig
+
+    return AcousticDynamicsConfig(**dict(dict(npx=n + 1, npy=n + 1, npz=nz, layout=layout, **DSW_OFF), **kw))
+
+
+def oracle_d_sw(doms, cfg, dc):
+    """the oracle's d_sw on copies of the case's inputs: the outputs per rank"""
+    from fv3_oracle import d_sw as o_dsw
+
+    col = o_dsw.get_column_namelist(cfg, dc.nz)
+    outs = []
+    for D, x in zip(doms, dc.ins):
+        w = {k: (x[k].copy() if k in x else np.zeros_like(x["u"])) for k in D_SW_ORDER}
+        w["zh"] = None
+        o_dsw.d_sw(D, cfg, col, *[w[k] for k in D_SW_ORDER], dc.dt)
+        outs.append(w)
+    return outs
+
+
+def dsw_case(shape, grids, c, axis=AXIS):
+    return DswCase(SHAPES[shape][0], grids, c.RADIUS, c.OMEGA, axis)
+
+
+def measure_d_sw(shape, axis=AXIS, ranks=None):
+    """the oracle's figures of pins 6 and 7 on one shape"""
+    n, layout, rk = SHAPES[shape]
+    part, grids, doms, c = make(n, layout, rk if ranks is None else ranks, DYN_NZ)
+    dc = dsw_case(shape, grids, c, axis)
+    outs = oracle_d_sw(doms, dyn_config(n, layout), dc)
+    if ranks is not None:  # the z-axis control of pin 7
+        return {"dt": dc.dt, **dc.wind_errors(outs), "tile0_east_class1": dc.wind_errors(outs, tile0_east)["class1"]}
+    return {"pin6": {"dt": dc.dt, **dc.scalar_errors(outs)}, "pin7": {"dt": dc.dt, **dc.wind_errors(outs)}}
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# pin 9: update_dz_d carries interface heights with the flow
+# ---------------------------------------------------------------------------------------------------------------------------
+ZS, DZ_LAYER, DZ_WAVE = 100.0, 2000.0, 300.0
+
+
+def height_field(p, nz=DYN_NZ):
+    """[..., nz + 1] interface heights: H_k + 300 m x smooth-like waves above the flat surface ZS"""
+    top = [ZS + DZ_LAYER * (nz - k) + DZ_WAVE * _wave(p, K_W, 0.5 * k) / 1.5 for k in range(nz)]
+    return np.stack(top + [np.full(p.shape[:-1], ZS)], -1)
+
+
+class HeightCase:
+    """per rank: zh [i, j, nz + 1], zs [i, j, 1], the exact swept areas xfx / yfx and the Courant numbers crx / cry = area over the upwind cell's
+    (as BellCase) on nz levels"""
+
+    def __init__(self, n, grids, a, nz=DYN_NZ):
+        self.n, self.grids, self.nz = n, grids, nz
+        self.flow = Flow(a)
+        self.dt = dyn_dt(n, self.flow)
+        self.G = [Geometry(g) for g in grids]
+        self.ins = []
+        for g, G in zip(grids, self.G):
+            sx, sy = self.flow.swept(G, self.dt)
+            ux, uy = upwind_area(g, sx, sy)
+            self.ins.append({"zh": height_field(G.C, nz), "zs": np.full(G.C.shape[:2] + (1,), ZS), "xfx": levels(sx, nz + 1), "yfx": levels(sy, nz + 1),
+                             "crx": levels(sx / ux, nz + 1), "cry": levels(sy / uy, nz + 1)})
+
+    def errors(self, zhs, wss, way=1.0):
+        """(max |zh - exact| / 300 m over the interfaces above the surface, max |wsd| dt / ZS)"""
+        err = ws = 0.0
+        for G, zh, w in zip(self.G, zhs, wss):
+            got = np.asarray(zh, dtype=np.float64)[G.cells][..., : self.nz + 1]
+            require(np.all(np.isfinite(got)), "non-finite height")
+            want = height_field(self.flow.rotate_back(G.C[G.cells], way * self.dt), self.nz)
+            err = max(err, float(np.abs(got - want)[..., : self.nz].max()) / DZ_WAVE)
+            ws = max(ws, float(np.abs(np.asarray(w, dtype=np.float64)[G.cells]).max()) * self.dt / ZS)
+        return err, ws
+
+
+def oracle_heights(doms, grids, cfg, hc):
+    from fv3_oracle import d_sw as o_dsw
+    from fv3_oracle import nh as o_nh
+
+    col = o_dsw.get_column_namelist(cfg, hc.nz)
+    zhs, wss = [], []
+    for D, g, x in zip(doms, grids, hc.ins):
+        zh, ws = x["zh"].copy(), np.zeros_like(x["zs"])
+        o_nh.update_dz_d(D, cfg, col, g.dp_ref, x["zs"], zh, x["crx"].copy(), x["cry"].copy(), x["xfx"].copy(), x["yfx"].copy(), ws, hc.dt)
+        zhs.append(zh), wss.append(ws)
+    return zhs, wss
+
+
+def measure_heights(shape):
+    n, layout, ranks = SHAPES[shape]
+    part, grids, doms, c = make(n, layout, ranks, DYN_NZ)
+    hc = HeightCase(n, grids, c.RADIUS)
+    err, ws = hc.errors(*oracle_heights(doms, grids, dyn_config(n, layout), hc))
+    return {"dt": hc.dt, "zh": err, "ws": ws}
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# pin 8: the Riemann solvers relax a column to the closed-form hydrostatic thickness
+# ---------------------------------------------------------------------------------------------------------------------------
+RIEM_N, RIEM_LEVELS, RIEM_DT, RELAX_DT, RELAX_CALLS, P_SURFACE = 12, (8, 79), 20.0, 200.0, 30, 1.0e5
+
+
+class Columns:
+    """Dry columns at rest over a flat surface, [i, j, nz + 1] arrays (the last level of a layer field repeats): interfaces log-spaced from ptop to
+    about 1e5 Pa with every layer's log-thickness jittered by +-3 %, T = 250 + 30 sin(0.4 k), pt = T / pm^kappa, and the thickness the gas law asks
+    for, delz_eq = -(delp / g) R pt pm^(kappa - 1), pm = delp / delta ln pe.  spoil: "exponent" builds delz_eq with kappa for kappa - 1, "midpoint"
+    with the arithmetic mid-pressure for pm (the controls)."""
+
+    def __init__(self, g, c, nz, spoil=None, seed=5, dtype=np.float64):
+        rng = np.random.default_rng(seed)
+        shape = np.asarray(g.lon_agrid).shape
+        self.nz, self.ptop, self.c, self.dtype = nz, float(g.ptop), c, dtype
+        dln = np.log(P_SURFACE / self.ptop) / nz * rng.uniform(0.97, 1.03, shape + (nz,))
+        peln = np.log(self.ptop) + np.concatenate([np.zeros(shape + (1,)), np.cumsum(dln, 2)], 2)
+        pe = np.exp(peln)
+        pe[:, :, 0] = self.ptop
+        delp = np.diff(pe, axis=2)
+        pm = delp / np.diff(np.log(pe), axis=2)
+        T = 250.0 + 30.0 * np.sin(0.4 * np.arange(nz))
+        pt = T / pm**c.KAPPA
+        pm_built = 0.5 * (pe[:, :, 1:] + pe[:, :, :-1]) if spoil == "midpoint" else pm
+        delz = -(delp / c.GRAV) * c.RDGAS * pt * pm_built ** (c.KAPPA if spoil == "exponent" else c.KAPPA - 1.0)
+        self.delp, self.pt, self.delz_eq, self.pe = delp, pt, delz, pe
+        self.control = delz * rng.uniform(0.97, 1.03, delz.shape)
+
+    def _pad(self, a):
+        return np.concatenate([a, a[:, :, -1:]], 2).astype(self.dtype)
+
+    def fields(self, delz):
+        """the arguments of riem_solver3 / riem_solver_c for the thickness ``delz``, w = 0"""
+        nz, shape = self.nz, delz.shape[:2]
+        zh = np.concatenate([-np.cumsum(delz[:, :, ::-1], 2)[:, :, ::-1], np.zeros(shape + (1,))], 2)
+        z3, z2 = np.zeros(shape + (nz + 1,), dtype=self.dtype), np.zeros(shape + (1,), dtype=self.dtype)
+        return {"cappa": np.full_like(z3, self.c.KAPPA), "q_con": z3.copy(), "delp": self._pad(self.delp), "pt": self._pad(self.pt), "delz": self._pad(delz), "zh": zh.astype(self.dtype),
+                "w": z3.copy(), "zs": z2.copy(), "ws": z2.copy(), "pe": z3.copy(), "ppe": z3.copy(), "pk3": z3.copy(), "pk": z3.copy(), "peln": z3.copy()}
+
+
+def rel(got, want):
+    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
+    require(np.all(np.isfinite(got)), "non-finite")
+    return float(np.abs(got / want - 1.0).max())
+
+
+def riem_figures(col, cells, solve, which):
+    """The figures of pin 8 for one solver.  solve(fields, dt, last_call) runs one call in place on the dict of Columns.fields (riem_solver3: w, delz,
+    zh, pe, peln, pk, pk3 out; riem_solver_c: zh holds heights in and the geopotential out, pef in "pe") and returns nothing.
+    balanced: one call at RIEM_DT on delz_eq; control: the same call on delz_eq x uniform(0.97, 1.03); relax: RELAX_CALLS calls at RELAX_DT from the
+    control, each fed the heights (and for riem_solver3 the w) of the one before."""
+    nz, c = col.nz, col.c
+    K = cells + (slice(0, nz),)
+    K1 = cells + (slice(0, nz + 1),)
+    out = {}
+
+    def thickness(f):
+        z = np.asarray(f["zh"], dtype=np.float64)
+        return (z[:, :, 1:] - z[:, :, :-1])[K]
+
+    def call(f, dt, last):
+        """one call; riem_solver_c returns the geopotential, which goes back to heights for the next call and for ``thickness``"""
+        solve(f, dt, last)
+        if which == "c":
+            f["zh"] = (np.asarray(f["zh"], dtype=np.float64) / c.GRAV).astype(col.dtype)
+
+    hydro = col.ptop + np.concatenate([np.zeros(col.delp.shape[:2] + (1,)), np.cumsum(col.delp, 2)], 2)
+    for name, dz in (("balanced", col.delz_eq), ("control", col.control)):
+        f = col.fields(dz)
+        call(f, RIEM_DT, 1)
+        out[name + "_delz"] = rel(thickness(f), col.delz_eq[K])
+        if which == "3":
+            out[name + "_w"] = float(np.abs(np.asarray(f["w"], dtype=np.float64)[K]).max())
+            out[name + "_delz_field"] = rel(np.asarray(f["delz"])[K], col.delz_eq[K])
+            if name == "balanced":
+                out["pe"], out["peln"] = rel(f["pe"][K1], hydro[K1]), rel(f["peln"][K1], np.log(hydro[K1]))
+                out["pk"], out["pk3"] = rel(f["pk"][K1], hydro[K1] ** c.KAPPA), rel(f["pk3"][K1], hydro[K1] ** c.KAPPA)
+        else:
+            out[name + "_pef"] = rel(f["pe"][K1], hydro[K1])
+    f = col.fields(col.control)
+    for it in range(RELAX_CALLS):
+        call(f, RELAX_DT, 0)
+        if it == 9:
+            out["relax10_delz"] = rel(thickness(f), col.delz_eq[K])
+    out["relax_delz"] = rel(thickness(f), col.delz_eq[K])
+    if which == "3":
+        out["relax_w"] = float(np.abs(np.asarray(f["w"], dtype=np.float64)[K]).max())
+    return out
+
+
+def oracle_riem(D, col, which, p_fac):
+    from fv3_oracle import nh as o_nh
+
+    def solve3(f, dt, last):
+        o_nh.riem_solver3(D, bool(last), dt, f["cappa"], col.ptop, f["zs"], f["ws"], f["delz"], f["q_con"], f["delp"], f["pt"], f["zh"], f["pe"], f["ppe"], f["pk3"], f["pk"], f["peln"], f["w"], p_fac)
+
+    def solve_c(f, dt, last):
+        o_nh.riem_solver_c(D, dt, f["cappa"], col.ptop, f["zs"], f["ws"], f["pt"], f["q_con"], f["delp"], f["zh"], f["pe"], f["w"], p_fac)
+
+    return solve3 if which == "3" else solve_c
+
+
+def _riem_need(label, fig, bound):
+    def need(key, limit):
+        lim = limit if bound is None else 4.0 * bound[key]
+        require(np.isfinite(fig[key]) and fig[key] <= lim, f"{label}: {key} {fig[key]:.3e} above {lim:.3e}")
+
+    return need
+
+
+def check_balanced(label, fig, which, bound=None):
+    """pin 8 (a) on the figures of riem_figures; ``bound`` (fp32): the oracle's np.float32 figures, held to 4 x each"""
+    print(label, {k: f"{v:.2e}" for k, v in fig.items()})
+    need = _riem_need(label, fig, bound)
+    require(fig["control_delz"] > 5e-3, f"{label}: the control is not out of balance")
+    need("balanced_delz", 1e-12)
+    if which == "3":
+        require(fig["control_w"] > 1.0, f"{label}: the control does not move")
+        lim = 1e-9 * fig["control_w"] if bound is None else 4.0 * bound["balanced_w"]
+        require(fig["balanced_w"] <= lim, f"{label}: |w| {fig['balanced_w']:.3e} on the balanced column above {lim:.3e}")
+        need("balanced_delz_field", 1e-12)
+        for k in ("pe", "peln", "pk", "pk3"):
+            need(k, 1e-13)
+    else:
+        require(fig["control_pef"] > 5e-3, f"{label}: the control's pressure is hydrostatic")
+        need("balanced_pef", 1e-12)
+
+
+def check_relaxed(label, fig, which, bound=None):
+    """pin 8 (b)"""
+    need = _riem_need(label, fig, bound)
+    need("relax_delz", 1e-12)
+    if which == "3":
+        need("relax_w", 1e-10)
+
+
+def measure_riem(nz, dtype=np.float64, spoil=None):
+    part, grids, doms, c = make(RIEM_N, (1, 1), (0,), nz)
+    G = Geometry(grids[0])
+    col = Columns(grids[0], c, nz, spoil, dtype=dtype)
+    p_fac = dyn_config(RIEM_N, (1, 1), nz).p_fac
+    return {w: riem_figures(col, G.cells, oracle_riem(doms[0], col, w, p_fac), w) for w in ("3", "c")}
+
+
+def measure_dynamics():
+    """the oracle's figures of pins 6 - 9: {pin: {...}}"""
+    out = {"pin6": {}, "pin7": {}, "pin7_z": {}, "pin8": {}, "pin9": {}}
+    for shape in SHAPES:
+        m = measure_d_sw(shape)
+        out["pin6"][shape], out["pin7"][shape] = m["pin6"], m["pin7"]
+        out["pin9"][shape] = measure_heights(shape)
+        print(shape, m, out["pin9"][shape])
+    for shape in ("c24", "c48"):
+        out["pin7_z"][shape] = measure_d_sw(shape, Z_AXIS, ranks=(0,))
+        print("z axis", shape, out["pin7_z"][shape])
+    for nz in RIEM_LEVELS:
+        out["pin8"][f"nz{nz}"] = {"fp64": measure_riem(nz), "fp32": measure_riem(nz, np.float32)}
+        print("pin8", nz, out["pin8"][f"nz{nz}"])
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
 # the shapes, and the record mode: the numpy oracle's own error on every input, tests/golden/analytic_pins.json
 # ---------------------------------------------------------------------------------------------------------------------------
 # name: (cells per tile, layout, ranks)
@@ -605,6 +1084,18 @@ def record(path=GOLDEN):
         print(name, out["pin2"][name]["l2"], "n_split", ns)
     out["pin5a"] = {"K": measure_pgf_k()}
     print("pin5a", out["pin5a"])
+    out.update(measure_dynamics())
+    return write(out, path)
+
+
+def record_dynamics(path=GOLDEN):
+    """pins 6 - 9 alone, into the file as it stands (``--record dynamics``)"""
+    out = recorded()
+    out.update(measure_dynamics())
+    return write(out, path)
+
+
+def write(out, path):
     with open(path, "w") as f:
         json.dump(out, f, indent=1, sort_keys=True)
         f.write("\n")
@@ -622,6 +1113,6 @@ if __name__ == "__main__":
         if p not in sys.path:
             sys.path.insert(0, p)
     if "--record" in sys.argv:
-        record()
+        record_dynamics() if "dynamics" in sys.argv else record()
     else:
         print(__doc__)
