@@ -99,6 +99,11 @@ typedef struct {
   int32_t hord_dp, hord_mt, hord_tm, hord_vt;
   int32_t nord, n_sponge;
   int32_t do_vort_damp, rf_fast, hydrostatic, use_logp, grid_type;
+  /* non-zero: the grid is a stretched (Schmidt-transformed) cubed sphere and the divergence damping coefficient is
+   * da_min * d4_bg^(nord+1) instead of (da_min_c * d4_bg)^(nord+1).  The geometry itself arrives in fv3_griddata; a stretched
+   * geometry with this flag 0 is legal.  (Takes the padding the 13 preceding int32 left: size and the offsets of the doubles
+   * are unchanged.) */
+  int32_t stretched_grid;
   double a_imp, beta, p_fac;
   double d2_bg, d2_bg_k1, d2_bg_k2, d4_bg, dddmp, d_con, d_ext, delt_max, ke_bg, vtdm4;
   double rf_cutoff, tau;

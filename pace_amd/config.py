@@ -68,6 +68,8 @@ class AcousticDynamicsConfig:
     hydrostatic: bool = False
     grid_type: int = 0
     nested: bool = False
+    # the grid went through a Schmidt transform: divergence damping takes dd8 = da_min * d4_bg^(nord+1) instead of
+    # (da_min_c * d4_bg)^(nord+1) (FV3 sw_core); the geometry itself arrives with the grids (pace_amd.grid.SchmidtTransform)
     stretched_grid: bool = False
     # transport
     hord_dp: int = 6
@@ -119,8 +121,8 @@ class AcousticDynamicsConfig:
             bad.append("use_logp")
         if self.grid_type != 0:
             bad.append("grid_type!=0")
-        if self.nested or self.stretched_grid:
-            bad.append("nested/stretched grid")
+        if self.nested:
+            bad.append("nested grid")
         for h in ("hord_dp", "hord_mt", "hord_tm", "hord_vt"):
             if getattr(self, h) not in (5, 6):
                 bad.append(f"{h}={getattr(self, h)} (5 or 6)")

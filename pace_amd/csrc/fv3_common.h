@@ -202,7 +202,7 @@ struct DampTables {
   const Real *tp_t;   // (damp_t  * da_min)^(nord_t+1)   fv_tp_2d of q_con
   const Real *d6_w;   // (damp_w  * da_min_c)^(nord_w+1) del6_vt_flux of w
   const Real *d6_vt;  // (damp_vt * da_min_c)^(nord_v+1) del6_vt_flux of vorticity
-  const Real *dd8;    // (da_min_c * d4_bg)^(nord+1)     divergence damping
+  const Real *dd8;    // (da_min_c * d4_bg)^(nord+1)     divergence damping; cfg.stretched_grid: da_min * d4_bg^(nord+1)
 };
 
 // What fv3_acoustic_step tells an operator about the ONE call it is making (fv3_ctx::seq, installed and taken back by SeqScope in fv3_step.hip).

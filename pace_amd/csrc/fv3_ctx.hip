@@ -365,9 +365,12 @@ int fv3_ctx_create(fv3_ctx **out, const fv3_gridspec *spec, const fv3_griddata *
       tp_t[k] = (Real)std::pow(c->damp_t_h[k] * grid->da_min, (double)(c->nord_t_h[k] + 1));
       d6_w[k] = (Real)std::pow(c->damp_w_h[k] * grid->da_min_c, (double)(c->nord_w_h[k] + 1));
       d6_vt[k] = (Real)std::pow(c->damp_vt_h[k] * grid->da_min_c, (double)(c->nord_v_h[k] + 1));
-      dd8[k] = (Real)std::pow(grid->da_min_c * cfg->d4_bg, (double)(c->nord_h[k] + 1));
+      // divergence damping: (da_min_c * d4_bg)^(nord + 1), on a stretched grid da_min * d4_bg^(nord + 1) (FV3 sw_core)
+      dd8[k] = cfg->stretched_grid ? (Real)(grid->da_min * std::pow(cfg->d4_bg, (double)(c->nord_h[k] + 1)))
+                                   : (Real)std::pow(grid->da_min_c * cfg->d4_bg, (double)(c->nord_h[k] + 1));
       // the tables are formed in double and stored as Real: in the fp32 build (da_min_c * d4_bg)^(nord + 1) leaves the
-      // float range on coarse grids (C48 and coarser: ~(6e9)^4) -- refuse instead of producing NaN states later
+      // float range on coarse grids (C48 and coarser: ~(6e9)^4) -- refuse instead of producing NaN states later.  The test is
+      // on the values of the forms in force: the stretched form of dd8 stays far inside the range
       if (!std::isfinite((double)tp_vt[k]) || !std::isfinite((double)tp_t[k]) || !std::isfinite((double)d6_w[k]) || !std::isfinite((double)d6_vt[k]) ||
           !std::isfinite((double)dd8[k])) {
         fv3_ctx_destroy(c);

@@ -212,7 +212,7 @@ void dsw_pair_march(fv3_ctx *c, fv3_stream_t s, const DswScalars &a, int role, i
 struct WindStage {
   const Real *u, *v, *uc, *vc, *divgd;
   Real *ke, *vdamp, *wk, *dnew;
-  const Real *dd8;  // per-level (da_min_c * d4_bg)^(nord+1)
+  const Real *dd8;  // per-level (da_min_c * d4_bg)^(nord+1); cfg.stretched_grid: da_min * d4_bg^(nord+1)
   Real dt, dddmp;
   int hord;
   bool store_dn;

@@ -24,7 +24,10 @@ The number of steps comes from ``seconds`` / ``minutes`` / ``hours`` / ``days`` 
 the reference [REF driver/pace/driver/driver.py:305-337 (total_time / n_steps)].
 
 Keys read from the yaml: ``nx_tile, nz, layout, dt_atmos, seconds|minutes|hours|days,
-dycore_config.*`` (the fields of ``AcousticDynamicsConfig``), ``stencil_config.compilation_config.
+grid_config`` (``type: generated`` with ``config.{stretch_factor, lon_target, lat_target}``: a factor other than 1 runs on the
+Schmidt-transformed grid with ``stretched_grid`` set, and the start-up line and the json ``setup`` say ``"grid": {"stretch_factor": ..,
+"lon_target": .., "lat_target": ..}``, otherwise ``"grid": "uniform"``; another ``type`` or ``grid_type != 0`` is refused),
+``dycore_config.*`` (the fields of ``AcousticDynamicsConfig``), ``stencil_config.compilation_config.
 {backend, device_sync}``, ``initialization.type`` (``analytic``/anything else -> the synthetic
 recipe of SURVEY §8d; the analytic baroclinic state is not part of this build and the driver says
 so).  ``backend`` values other than ``hip:gfx950`` are reported and replaced: this build has one
@@ -66,6 +69,30 @@ def resolve_sat_adj(option: str, sat_block: dict, moist: bool) -> bool:
     return bool(want and moist)
 
 
+def read_grid_config(block) -> dict:
+    """The yaml's ``grid_config`` block [REF driver/pace/driver/grid.py:94-96, 288-319] -> ``{"stretch_factor", "lon_target",
+    "lat_target"}`` (the reference's defaults where a key is absent; factor 1 = the uniform grid).  This build generates its grids:
+    any other ``type``, and a ``grid_type`` other than 0, is refused instead of being ignored."""
+    block = block or {}
+    kind = block.get("type", "generated")
+    if kind != "generated":
+        raise ValueError(f"grid_config.type: {kind!r} is not available in this build: it generates its grids (type: generated) and reads none.")
+    cfg = block.get("config") or {}
+    if int(cfg.get("grid_type", 0) or 0) != 0:
+        raise ValueError(f"grid_config.config.grid_type: {cfg['grid_type']} is not available in this build: the grid is the cubed sphere (grid_type: 0), uniform or stretched.")
+    return {"stretch_factor": float(cfg.get("stretch_factor", 1.0)), "lon_target": float(cfg.get("lon_target", 350.0)), "lat_target": float(cfg.get("lat_target", -90.0))}
+
+
+def grid_entry(grid: dict):
+    """What the start-up line and the json say about the grid: the three numbers of a stretched grid, or ``"uniform"``."""
+    return dict(grid) if float(grid["stretch_factor"]) != 1.0 else "uniform"
+
+
+def harness_grid_kwargs(grid: dict) -> dict:
+    """The ``DycoreHarness`` keywords of the yaml's grid: none for the uniform grid; the harness sets the config's ``stretched_grid`` with them."""
+    return dict(grid) if float(grid["stretch_factor"]) != 1.0 else {}
+
+
 def load_config(path: str):
     with open(path) as f:
         y = yaml.safe_load(f)
@@ -99,6 +126,7 @@ def load_config(path: str):
         output_initial_state=bool(y.get("output_initial_state", False)),
         output_frequency=int(y.get("output_frequency", 1)),
         start_time=(((y.get("initialization") or {}).get("config") or {}).get("start_time", None)),
+        grid=read_grid_config(y.get("grid_config")),
     )
     return run, dy, ignored
 
@@ -179,7 +207,10 @@ def main(argv=None):
         sys.exit("--neg-adj needs --moist: neg_adj3 works on the six water species of the moist step")
     if a.sat_adj == "on" and not a.moist:
         sys.exit("--sat-adj on needs --moist: the saturation adjustment works on the six water species of the moist step")
-    run, dy, ignored = load_config(a.config)
+    try:
+        run, dy, ignored = load_config(a.config)
+    except ValueError as e:
+        sys.exit(str(e))
     if a.moist:
         if run["nwat"] is None or int(run["nwat"]) != 6:
             sys.exit(f"--moist needs dycore_config.nwat: 6 in the yaml (it has nwat: {run['nwat']}): moist_cv is built for the six-species formula only")
@@ -219,6 +250,8 @@ def main(argv=None):
     say(f'"sat_adj": {str(sat_adj).lower()}' + ("" if a.sat_adj == "yaml" else f" (--sat-adj {a.sat_adj})")
         + ("  (fv_sat_adj on the six water species inside every remap, between the fill and moist_cv)" if sat_adj
            else "  (no phase changes; --moist with do_sat_adj: true in the yaml or --sat-adj on: fv_sat_adj inside every remap)"))
+    say(f'"grid": {json.dumps(grid_entry(run["grid"]))}' + ("  (Schmidt transform of the generated corner positions; divergence damping in its stretched form)" if grid_entry(run["grid"]) != "uniform"
+                                                            else "  (grid_config.config.stretch_factor / lon_target / lat_target: a grid refined about a target point)"))
     if run["init"] == "analytic" and str(run["case"]).startswith("baroclinic"):
         init = "baroclinic"
         say("initialization: JW2006 baroclinic wave (pace_amd.init.baroclinic_state; restated from the paper, see its docstring)")
@@ -240,7 +273,7 @@ def main(argv=None):
     kw = {k: dy[k] for k in ("k_split", "n_split") if k in dy}
     h = DycoreHarness(nx_tile=run["nx_tile"], nz=run["nz"], layout=run["layout"], dt_atmos=run["dt_atmos"], world_size=world, proc=rank,
                       device=f"cuda:{local_rank}", dtype=dtype, verbose=(rank == 0), init=init, config_overrides={k: v for k, v in dy.items() if k not in ("k_split", "n_split", "fill")},
-                      n_tracers=a.tracers, hord_tr=int(dy.get("hord_tr", 8)), remap=a.remap, fill=fill, latlon_winds=a.latlon_winds, temperature=a.temperature, moist=a.moist, neg_adj=a.neg_adj, sat_adj=sat_adj, sat_adjust_config=sat_cfg, **kw)
+                      n_tracers=a.tracers, hord_tr=int(dy.get("hord_tr", 8)), remap=a.remap, fill=fill, latlon_winds=a.latlon_winds, temperature=a.temperature, moist=a.moist, neg_adj=a.neg_adj, sat_adj=sat_adj, sat_adjust_config=sat_cfg, **harness_grid_kwargs(run["grid"]), **kw)
     if run["device_sync"]:
         h.sf.set_device_sync(True)
     if a.restart:
@@ -248,6 +281,7 @@ def main(argv=None):
 
         try:
             restart.check_pt_form(h.layout.local_ranks, a.restart, a.temperature)
+            restart.check_grid(h.layout.local_ranks, a.restart, h.stretch)
         except ValueError as e:
             sys.exit(f"--restart: {e}")
         restart.load_state(h.state, h.layout.local_ranks, a.restart, extra=h.tracers)
@@ -305,7 +339,7 @@ def main(argv=None):
     if a.save_restart:
         from . import restart
 
-        restart.save_state(h.state, h.layout.local_ranks, a.save_restart, extra=h.tracers, **({"pt_form": restart.PT_TEMPERATURE} if a.temperature else {}))
+        restart.save_state(h.state, h.layout.local_ranks, a.save_restart, extra=h.tracers, stretch=h.stretch, **({"pt_form": restart.PT_TEMPERATURE} if a.temperature else {}))
         say(f"restart files written to {a.save_restart}")
     # per reference rank (the ranks a process owns step together: they share its clocks)
     local = {r: {n: [t.get(n, 0.0) for t in times_per_step] for n in times_per_step[0]} for r in h.layout.local_ranks}
@@ -327,7 +361,7 @@ def main(argv=None):
         sdpd = run["dt_atmos"] / mean
         out = a.out or f"{run['experiment']}_fv3_mi355x.json"
         json.dump({"setup": {"experiment": run["experiment"], "nx_tile": run["nx_tile"], "nz": run["nz"], "layout": list(run["layout"]), "dt_atmos": run["dt_atmos"],
-                             "k_split": h.cfg.k_split, "n_split": h.cfg.n_split, "n_gpus": world, "backend": "hip:gfx950", "dycore_only": True, "acoustic_only": not (a.tracers or a.remap), "tracers": a.tracers, "remap": bool(a.remap), "fill": fill, "pt": pt_form, "thermodynamics": thermo, "neg_adj": bool(a.neg_adj), "sat_adj": sat_adj, "finite": ok,
+                             "k_split": h.cfg.k_split, "n_split": h.cfg.n_split, "n_gpus": world, "backend": "hip:gfx950", "dycore_only": True, "acoustic_only": not (a.tracers or a.remap), "tracers": a.tracers, "remap": bool(a.remap), "fill": fill, "pt": pt_form, "thermodynamics": thermo, "neg_adj": bool(a.neg_adj), "sat_adj": sat_adj, "grid": grid_entry(run["grid"]), "finite": ok,
                              "note": ("a step here is k_split AcousticDynamics calls; the reference's dycore_only mainloop (DynamicalCore.step_dynamics) also runs tracer "
                                       "advection and the Lagrangian-to-Eulerian remap (--tracers N --remap add them): not comparable with the reference's 'mainloop' timer")
                              if not (a.tracers and a.remap) else

@@ -88,7 +88,7 @@ class AcousticDynamics:
         damping_coefficients=None,
         grid_type: int = 0,
         nested: bool = False,
-        stretched_grid: bool = False,
+        stretched_grid: Optional[bool] = None,
         config: Optional[AcousticDynamicsConfig] = None,
         phis: Optional[Quantity] = None,
         wsd: Optional[Quantity] = None,
@@ -99,6 +99,8 @@ class AcousticDynamics:
         self.sf = stencil_factory
         self.qf = quantity_factory or stencil_factory.quantity_factory
         self.config = (config or stencil_factory.config).validate()
+        # (None: the config's flag; either way it has to be the form the context's divergence damping table was made in)
+        st.check_stretched_grid("AcousticDynamics", self.config.stretched_grid if stretched_grid is None else stretched_grid, stencil_factory)
         self.checkpointer = checkpointer
         self.native = True  # sequence the call with fv3_acoustic_step (C) rather than the Python twin below
         self.grid_data = grid_data

@@ -105,6 +105,62 @@ def lonlat(p):
 
 
 # ----------------------------------------------------------------------------
+# Schmidt transform (stretched grid)
+# ----------------------------------------------------------------------------
+@dataclass(frozen=True)
+class SchmidtTransform:
+    """Refinement of the cubed sphere about a target point: FV3's ``direct_transform`` as the reference driver applies it to the
+    generated corner positions [REF driver/pace/driver/grid.py:94-96, 118-121, 288-319].  Angles in degrees; the defaults are the
+    reference's and leave the grid as it is (``stretch_factor == 1``)."""
+
+    stretch_factor: float = 1.0
+    lon_target: float = 350.0
+    lat_target: float = -90.0
+
+    @property
+    def active(self) -> bool:
+        return float(self.stretch_factor) != 1.0
+
+    @property
+    def key(self) -> Tuple[float, float, float]:
+        return (float(self.stretch_factor), float(self.lon_target), float(self.lat_target))
+
+    def as_dict(self) -> Dict[str, float]:
+        return {"stretch_factor": float(self.stretch_factor), "lon_target": float(self.lon_target), "lat_target": float(self.lat_target)}
+
+    def __call__(self, p: np.ndarray) -> np.ndarray:
+        """Unit vectors ``p[..., 3]`` -> the transformed unit vectors.  Step 1 moves every point along its meridian away from the
+        south pole, sin(lat') = (D + sin(lat)) / (1 + D sin(lat)) with D = (1 - c^2) / (1 + c^2), i.e. tan(theta' / 2) =
+        tan(theta / 2) / c for the angular distance theta from the south pole; step 2 rotates the south pole to the target."""
+        if not self.active:
+            return p
+        c2 = float(self.stretch_factor) ** 2
+        D = (1.0 - c2) / (1.0 + c2)
+        lon_p, lat_p = np.deg2rad(float(self.lon_target)), np.deg2rad(float(self.lat_target))
+        sp, cp = np.sin(lat_p), np.cos(lat_p)
+        lon = np.arctan2(p[..., 1], p[..., 0])
+        sin_lat = np.clip(p[..., 2], -1.0, 1.0)
+        sin_t = (D + sin_lat) / (1.0 + D * sin_lat)
+        # cos(lat') from the same closed form (no cancellation near the poles): cos(lat) sqrt(1 - D^2) / (1 + D sin(lat))
+        cos_t = np.sqrt(p[..., 0] ** 2 + p[..., 1] ** 2) * np.sqrt(1.0 - D * D) / (1.0 + D * sin_lat)
+        sin_o = -(sp * sin_t + cp * cos_t * np.cos(lon))
+        # lon'' = lon_p + atan2(y_r, x_r); (x_r, y_r, sin_o) has unit length, so the unit vector of (lon'', lat'') is formed from
+        # the two arguments directly instead of through asin / atan2 and back (no loss of accuracy near the rotated poles)
+        y_r = -cos_t * np.sin(lon)
+        x_r = -sin_t * cp + cos_t * sp * np.cos(lon)
+        pole = (1.0 - np.abs(sin_o)) < 1.0e-7  # the pole itself: lon'' = 0
+        out = np.empty_like(p)
+        out[..., 0] = np.where(pole, np.hypot(x_r, y_r), np.cos(lon_p) * x_r - np.sin(lon_p) * y_r)
+        out[..., 1] = np.where(pole, 0.0, np.sin(lon_p) * x_r + np.cos(lon_p) * y_r)
+        out[..., 2] = sin_o
+        return _normalize(out)
+
+
+def _active(stretch: Optional["SchmidtTransform"]) -> Optional["SchmidtTransform"]:
+    return stretch if (stretch is not None and stretch.active) else None
+
+
+# ----------------------------------------------------------------------------
 # eta levels
 # ----------------------------------------------------------------------------
 def load_eta79() -> Tuple[np.ndarray, np.ndarray]:
@@ -173,6 +229,8 @@ class GridData:
     # a2b_ord4 corner extrapolation factors x1/(x2-x1), 3 per cube corner (sw, se, ne, nw)
     corner_extrap: np.ndarray
     fields: Dict[str, np.ndarray]
+    # the Schmidt transform the corner positions went through (None: the uniform grid)
+    stretch: Optional["SchmidtTransform"] = None
 
     def __getattr__(self, name):
         f = self.__dict__.get("fields")
@@ -210,8 +268,9 @@ class DampingCoefficients:
 # ----------------------------------------------------------------------------
 # generator
 # ----------------------------------------------------------------------------
-def _corner_positions(part: CubedSpherePartitioner, rank: int, nh: int) -> np.ndarray:
-    """Unit vectors of the grid corners of a rank incl. halo, shape (nx+2nh+1, ny+2nh+1, 3)."""
+def _corner_positions(part: CubedSpherePartitioner, rank: int, nh: int, stretch: Optional[SchmidtTransform] = None) -> np.ndarray:
+    """Unit vectors of the grid corners of a rank incl. halo, shape (nx+2nh+1, ny+2nh+1, 3).  ``stretch`` is applied pointwise to
+    the finished array: compute points, edge halos and the cube-corner fill blocks alike."""
     n = part.nx_tile
     tile = part.tile_index(rank)
     x0, y0 = part.origin(rank)
@@ -241,6 +300,8 @@ def _corner_positions(part: CubedSpherePartitioner, rank: int, nh: int) -> np.nd
             tr = edge_transform(tile, d)
             x2, y2 = tr.apply(Xs[m], Ys[m], n)
             P[m] = tile_point(tr.tile, x2, y2, n)
+    if _active(stretch) is not None:
+        P = stretch(P)
     return P
 
 
@@ -265,11 +326,17 @@ def make_grid(
     bk: Optional[np.ndarray] = None,
     da_min: Optional[float] = None,
     da_min_c: Optional[float] = None,
+    stretch: Optional[SchmidtTransform] = None,
 ) -> GridData:
     """Metric terms of one rank.  ``da_min``/``da_min_c`` are global minima
-    (the one reduction of grid setup [SURVEY A.15]); when None they are taken
-    from the analytic symmetry of the grid (all six tiles are congruent, so the
-    minimum over tile 0 is the global minimum)."""
+    (the one reduction of grid setup [SURVEY A.15]); when None they come from
+    ``global_area_minima``: on the uniform grid from its analytic symmetry (all
+    six tiles are congruent, so a corner patch of tile 0 decides), with a
+    ``stretch`` from a scan of the six tiles.  ``stretch`` (a SchmidtTransform
+    with ``stretch_factor != 1``) moves the corner positions; every metric term
+    is derived from them as on the uniform grid, so the tiles are then neither
+    congruent nor symmetric in themselves."""
+    stretch = _active(stretch)
     c = constants or get_constants()
     R = c.RADIUS
     nh = n_halo
@@ -277,7 +344,7 @@ def make_grid(
     n = part.nx_tile
     x0, y0 = part.origin(rank)
     flags = part.on_tile_edges(rank)
-    P = _corner_positions(part, rank, nh)
+    P = _corner_positions(part, rank, nh, stretch)
     shape = (nx + 2 * nh + 1, ny + 2 * nh + 1)
     f: Dict[str, np.ndarray] = {}
 
@@ -543,7 +610,7 @@ def make_grid(
         ak, bk = make_eta(nz)
     ks = int(np.sum(bk[1:] == 0.0))  # number of pure-pressure layers
     if da_min is None or da_min_c is None:
-        gm = global_area_minima(part.nx_tile, c, nh)
+        gm = global_area_minima(part.nx_tile, c, nh, stretch=stretch)
         da_min = gm[0] if da_min is None else da_min
         da_min_c = gm[1] if da_min_c is None else da_min_c
     return GridData(
@@ -567,17 +634,55 @@ def make_grid(
         edge_n=edge_n,
         corner_extrap=corner_extrap,
         fields=f,
+        stretch=stretch,
     )
 
 
-_AREA_MIN_CACHE: Dict[Tuple[int, str, int], Tuple[float, float]] = {}
+_AREA_MIN_CACHE: Dict[tuple, Tuple[float, float]] = {}
 
 
-def global_area_minima(nx_tile: int, c: ConstantSet, nh: int = 3) -> Tuple[float, float]:
+def _stretched_area_minima(nx_tile: int, c: ConstantSet, nh: int, stretch: SchmidtTransform) -> Tuple[float, float]:
+    """Minima of ``area`` / ``area_c`` over the compute domains of all six tiles of a stretched grid.  Areas only: the cells and
+    the dual cells are formed from the corner positions exactly as ``make_grid`` forms them (interior quads of the four centres,
+    twice the half cell on a tile edge, three kites at a cube corner), on whole tiles, so that the two numbers do not depend on
+    the decomposition that asks for them."""
+    R = c.RADIUS
+    part = CubedSpherePartitioner(nx_tile, (1, 1))
+    n = nx_tile
+    a_min, ac_min = np.inf, np.inf
+    for tile in range(6):
+        P = _corner_positions(part, tile, 0, stretch)  # (n + 1, n + 1, 3): the tile's own corners
+        A = _normalize(P[:-1, :-1] + P[1:, :-1] + P[:-1, 1:] + P[1:, 1:])
+        a_min = min(a_min, float((R * R * quad_area(P[:-1, :-1], P[1:, :-1], P[1:, 1:], P[:-1, 1:])).min()))
+        if n > 1:
+            ac_min = min(ac_min, float((R * R * np.abs(quad_area(A[:-1, :-1], A[1:, :-1], A[1:, 1:], A[:-1, 1:]))).min()))
+            jr = np.arange(1, n)
+            for ii, ci in ((0, 0), (n, n - 1)):
+                p1, p4 = _mid(P[ii, jr - 1], P[ii, jr]), _mid(P[ii, jr], P[ii, jr + 1])
+                ac_min = min(ac_min, float((2.0 * R * R * np.abs(quad_area(p1, A[ci, jr - 1], A[ci, jr], p4))).min()))
+                p1, p4 = _mid(P[jr - 1, ii], P[jr, ii]), _mid(P[jr, ii], P[jr + 1, ii])
+                ac_min = min(ac_min, float((2.0 * R * R * np.abs(quad_area(p1, A[jr - 1, ci], A[jr, ci], p4))).min()))
+        for ii, ci, si in ((0, 0, 1), (n, n - 1, -1)):
+            for jj, cj, sj in ((0, 0, 1), (n, n - 1, -1)):
+                px, py = _mid(P[ii, jj], P[ii + si, jj]), _mid(P[ii, jj], P[ii, jj + sj])
+                ac_min = min(ac_min, float(3.0 * R * R * abs(quad_area(P[ii, jj], px, A[ci, cj], py))))
+    return a_min, ac_min
+
+
+def global_area_minima(nx_tile: int, c: ConstantSet, nh: int = 3, stretch: Optional[SchmidtTransform] = None) -> Tuple[float, float]:
     """(da_min, da_min_c): global minima of ``area`` and ``area_c`` over compute
-    domains.  All six tiles are congruent, so tile 0 alone decides; computed
-    once per resolution from a 1x1-layout tile with explicit values (not by
-    recursion into make_grid's default)."""
+    domains.  On the uniform grid all six tiles are congruent, so tile 0 alone
+    decides; computed once per resolution from a 1x1-layout tile with explicit
+    values (not by recursion into make_grid's default).  With a ``stretch`` the
+    smallest cell is not known a priori (the gnomonic minimum sits at the tile
+    corners, the Schmidt factor is smallest at the target): all six tiles are
+    scanned, once per (resolution, constants, halo, stretch)."""
+    stretch = _active(stretch)
+    if stretch is not None:
+        skey = (nx_tile, c.name, nh) + stretch.key
+        if skey not in _AREA_MIN_CACHE:
+            _AREA_MIN_CACHE[skey] = _stretched_area_minima(nx_tile, c, nh, stretch)
+        return _AREA_MIN_CACHE[skey]
     key = (nx_tile, c.name, nh)
     if key not in _AREA_MIN_CACHE:
         # cell areas of the equal-edge gnomonic grid shrink monotonically towards the cube
@@ -597,5 +702,8 @@ def global_area_minima(nx_tile: int, c: ConstantSet, nh: int = 3) -> Tuple[float
     return _AREA_MIN_CACHE[key]
 
 
-def damping_coefficients(g: GridData) -> DampingCoefficients:
+def damping_coefficients(g: GridData, stretch: Optional[SchmidtTransform] = None) -> DampingCoefficients:
+    """``stretch``: the transform the caller believes ``g`` was made with; a grid made with another one is refused."""
+    if stretch is not None and _active(stretch) != g.stretch:
+        raise ValueError(f"damping_coefficients: the grid was made with stretch {g.stretch}, not {stretch}")
     return DampingCoefficients(g.del6_u, g.del6_v, g.divg_u, g.divg_v, g.da_min, g.da_min_c)

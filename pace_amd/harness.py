@@ -12,6 +12,8 @@ ends ``fv_dynamics`` (eastward / northward ``ua``, ``va``); ``temperature`` (nee
 diagnosed, ``vapor`` names the tracer that is the specific humidity; ``moist`` (needs ``temperature``) names the first six tracers
 after the water species and lets ``q_con`` / ``cappa`` follow them (``moist_cv`` in the preamble and in every remap); ``neg_adj``
 (needs ``moist``) ends the thermodynamic part of the step with FV3's ``neg_adj3`` on the temperature and the six species.
+``stretch_factor`` / ``lon_target`` / ``lat_target`` (degrees; the reference's ``grid_config.config`` keys): a factor other than 1 refines the
+grid about the target with a Schmidt transform (``pace_amd.grid.SchmidtTransform``) and sets ``stretched_grid`` in the config.
 """
 from __future__ import annotations
 
@@ -25,7 +27,7 @@ from .config import AcousticDynamicsConfig
 from .constants import get_constants
 from .context import StencilFactory
 from .dyn_core import STATE_NAMES, AcousticDynamics, DycoreState
-from .grid import make_grid
+from .grid import SchmidtTransform, make_grid
 from .halo import Layout
 from .init import synthetic_state, synthetic_state_device
 from .topology import CubedSpherePartitioner
@@ -83,6 +85,9 @@ class DycoreHarness:
         neg_adj: bool = False,
         sat_adj: bool = False,
         sat_adjust_config=None,
+        stretch_factor: float = 1.0,
+        lon_target: float = 350.0,
+        lat_target: float = -90.0,
         _testing_token=None,
     ):
         if fill and not remap:
@@ -107,13 +112,17 @@ class DycoreHarness:
         self.moist = bool(moist)
         self.c = get_constants()
         self.part = CubedSpherePartitioner(nx_tile, tuple(layout))
+        # a stretch factor other than 1 gives the Schmidt-transformed grid AND the stretched form of the divergence damping
+        # (the two are separate inputs below this class: make_grid's stretch, the config's stretched_grid)
+        stretch = SchmidtTransform(float(stretch_factor), float(lon_target), float(lat_target))
+        self.stretch = stretch if stretch.active else None
         self.cfg = AcousticDynamicsConfig(npx=nx_tile + 1, npy=nx_tile + 1, npz=nz, layout=tuple(layout), dt_atmos=dt_atmos, k_split=k_split, n_split=n_split,
-                                          **{**(config_overrides or {}), "fill": bool(fill)})
+                                          **{**(config_overrides or {}), "fill": bool(fill), **({"stretched_grid": True} if self.stretch else {})})
         self.layout = Layout(self.part, world_size, proc)
         self.layout.group = group
         self.layout.loopback = bool(loopback)  # this process plays `proc` of `world_size` alone, its messages looped back (timing runs)
         t0 = time.time()
-        self.grids = [make_grid(self.part, r, nz=nz, ak=ak, bk=bk) for r in self.layout.local_ranks]
+        self.grids = [make_grid(self.part, r, nz=nz, ak=ak, bk=bk, stretch=self.stretch) for r in self.layout.local_ranks]
         if verbose:
             print(f"[harness] grid for ranks {self.layout.local_ranks} in {time.time() - t0:.1f}s", flush=True)
         self.sf = StencilFactory(self.grids, self.cfg, self.c, backend=backend, device=device, dtype=dtype, _testing_token=_testing_token)

@@ -60,7 +60,7 @@ class fv3_griddata(C.Structure):
     ]
 
 
-CFG_INT = "n_split k_split hord_dp hord_mt hord_tm hord_vt nord n_sponge do_vort_damp rf_fast hydrostatic use_logp grid_type".split()
+CFG_INT = "n_split k_split hord_dp hord_mt hord_tm hord_vt nord n_sponge do_vort_damp rf_fast hydrostatic use_logp grid_type stretched_grid".split()
 CFG_DBL = "a_imp beta p_fac d2_bg d2_bg_k1 d2_bg_k2 d4_bg dddmp d_con d_ext delt_max ke_bg vtdm4 rf_cutoff tau".split()
 
 

@@ -49,11 +49,13 @@ PT_TEMPERATURE = "temperature"
 
 
 def save_state(state: DycoreState, local_ranks: Sequence[int], restart_path: str = "RESTART", names: Optional[Iterable[str]] = None, extra=None,
-               pt_form: Optional[str] = None) -> list:
+               pt_form: Optional[str] = None, stretch=None) -> list:
     """Write one file per local rank; returns the paths.  ``local_ranks[i]`` is the global rank of sub-domain i.
     ``extra``: {name: Quantity} written beside the state's fields (the tracers).  ``pt_form``: what ``pt`` holds, written as the
     global attribute ``pt_form`` -- ``"temperature"`` (K, the reference's contract: a state stepped through ``DynamicalCore``) or
-    None: no attribute, ``pt`` is the acoustic loop's ``T_v / pkz`` (the files of the default mode, unchanged)."""
+    None: no attribute, ``pt`` is the acoustic loop's ``T_v / pkz`` (the files of the default mode, unchanged).  ``stretch``: the
+    ``pace_amd.grid.SchmidtTransform`` of a stretched grid, written as the global attributes ``stretch_factor``, ``lon_target``,
+    ``lat_target``; None (the uniform grid): no attributes, the files are what they were."""
     from scipy.io import netcdf_file
 
     os.makedirs(restart_path, exist_ok=True)
@@ -67,6 +69,9 @@ def save_state(state: DycoreState, local_ranks: Sequence[int], restart_path: str
             f.rank = np.int32(rank)
             if pt_form is not None:
                 f.pt_form = str(pt_form)
+            if stretch is not None and stretch.active:
+                for k, v in stretch.as_dict().items():
+                    setattr(f, k, np.float64(v))
             for n, q in fields:
                 a = q.numpy(i)  # (i, j[, k]) host copy of the full storage
                 dims = []
@@ -107,6 +112,38 @@ def check_pt_form(local_ranks: Sequence[int], restart_path: str, temperature: bo
             raise ValueError(f"{_path(restart_path, rank)} has no pt_form = \"temperature\" attribute: its pt is the acoustic loop's T_v / pkz, and a --temperature run restarts only from files written by one.")
         if not temperature and form is not None:
             raise ValueError(f"{_path(restart_path, rank)} has pt_form = \"{form}\": its pt is a temperature in K, and a run without --temperature restarts only from files written without it.")
+
+
+GRID_ATTRS = ("stretch_factor", "lon_target", "lat_target")
+
+
+def grid_of(restart_path: str, rank: int):
+    """(stretch_factor, lon_target, lat_target) of one rank's restart file, or None: the file carries no such attributes (uniform grid)."""
+    p = _path(restart_path, rank)
+    if not os.path.exists(p):
+        raise FileNotFoundError(f"{p}: no restart file for rank {rank}")
+    with open(p, "rb") as fh:
+        magic = fh.read(4)
+    if magic[:3] != b"CDF":  # (a reference file: it does not say what grid it was written on)
+        return None
+    from scipy.io import netcdf_file
+
+    with netcdf_file(p, "r", mmap=False) as f:
+        v = [getattr(f, k, None) for k in GRID_ATTRS]
+    if v[0] is None:
+        return None
+    return tuple(float(np.asarray(x).ravel()[0]) for x in v)
+
+
+def check_grid(local_ranks: Sequence[int], restart_path: str, stretch=None) -> None:
+    """Refuse restart files written on another grid than the run's (``stretch``: its SchmidtTransform, None = uniform): one sentence, as a ``ValueError``."""
+    want = stretch.key if (stretch is not None and stretch.active) else None
+    for rank in local_ranks:
+        have = grid_of(restart_path, rank)
+        if have != want:
+            def say(g):
+                return "the uniform grid" if g is None else f"a grid stretched by {g[0]:g} about ({g[1]:g}, {g[2]:g})"
+            raise ValueError(f"{_path(restart_path, rank)} was written on {say(have)} and this run is on {say(want)}: a run restarts only from files of its own grid.")
 
 
 class MissingValuesError(RuntimeError):

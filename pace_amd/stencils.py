@@ -134,9 +134,18 @@ class AGrid2BGridFourthOrder(_Op):
         self.sf.call("a2b_ord4", qin.fref, qout.fref, int(kstart), int(self.nk if nk is None else nk), int(self.replace))
 
 
+def check_stretched_grid(who, stretched_grid, stencil_factory):
+    """The ``stretched_grid`` keyword of an operator against the flag its context was created with (the context formed the divergence
+    damping table in that form): None follows the context, anything else must agree."""
+    have = bool(stencil_factory.config.stretched_grid)
+    if stretched_grid is not None and bool(stretched_grid) != have:
+        raise ValueError(f"{who}(stretched_grid={bool(stretched_grid)}): the stencil factory's config has stretched_grid={have}, and its damping tables were formed for that.")
+
+
 class DGridShallowWaterLagrangianDynamics(_Op):
-    def __init__(self, stencil_factory, quantity_factory=None, grid_data=None, damping_coefficients=None, column_namelist=None, nested=False, stretched_grid=False, config=None):
+    def __init__(self, stencil_factory, quantity_factory=None, grid_data=None, damping_coefficients=None, column_namelist=None, nested=False, stretched_grid=None, config=None):
         super().__init__(stencil_factory, quantity_factory, grid_data)
+        check_stretched_grid("DGridShallowWaterLagrangianDynamics", stretched_grid, stencil_factory)
 
     def __call__(self, delpc, delp, pt, u, v, w, uc, vc, ua, va, divgd, mfx, mfy, cx, cy, crx, cry, xfx, yfx, q_con, zh, heat_source, diss_est, dt):
         a = (delpc, delp, pt, u, v, w, uc, vc, ua, va, divgd, mfx, mfy, cx, cy, crx, cry, xfx, yfx, q_con, zh, heat_source, diss_est)
