@@ -98,7 +98,7 @@ inline void fv3_stamp_touch(unsigned long long *, unsigned long long, int) {}
 // in the ISA: vmcnt(7) / vmcnt(2) at the top of the two-tracer marches): d_sw 52.6 vs 52.6 ms, update_dz_d 11.2 vs 11.1 on the same
 // box -- the stores are acknowledged long before the rows arrive, the drain costs nothing.  The conditional form is the default.
 #define FV3_TRASH_SLOTS 4096
-// element at a wave-uniform base + a per-lane byte offset of 32 bits (scalar-base addressing: see KW_ in fv3_nh.hip)
+// element at a wave-uniform base + a per-lane byte offset of 32 bits (scalar-base addressing: see KW_ in fv3_kwalk.h)
 template <class T>
 FV3_HD inline T *fv3_at(T *base, unsigned byte_off) {
   return (T *)((char *)base + byte_off);
@@ -218,7 +218,7 @@ struct fv3_seq_hints {
   // does not touch) RUNNING on the auxiliary stream when it returns (fv3_ctx::csw_pending); the sequencer joins them before riem_solver_c, the first reader
   bool csw_defer = false;
   // update_dz_d: it may leave its last kernel -- the bottom-up scan that keeps the marched interface heights dz_min apart and forms the surface vertical
-  // velocity -- to riem_solver3, whose wave form runs it as a pre-sweep of each column (fv3_nh.hip: PRE; fv3_ctx::dz_scan_src)
+  // velocity -- to riem_solver3, whose wave form runs it as a pre-sweep of each column (fv3_riem.hip: PRE; fv3_ctx::dz_scan_src)
   bool dz_scan = false;
   // d_sw: leave cx / cy alone -- crx / cry of every sub-step of a call stay in their own arrays (fv3_ctx::acc_slots) and cx / cy are formed ONCE, at the end of
   // the last d_sw of the call, as ((0 + s1) + s2) + ... in the order the read-modify-write of every sub-step would have used
@@ -291,8 +291,9 @@ struct fv3_ctx {
   int pp_n = 0;
   fv3_seq_hints seq;  // what fv3_acoustic_step says about the operator call it is making (fv3_step.hip: SeqScope); all defaults outside it
   bool csw_pending = false;  // c_sw under seq.csw_defer left stage D / E windows running on the auxiliary stream: the join (event 7, fv3_csw_join) is still owed
-  // Channel from update_dz_d to riem_solver3 (fv3_nh.hip), not a hint: update_dz_d under seq.dz_scan WRITES the marched heights of the scan it left undone
-  // (null: none) and dz_min; riem_solver3's wave form READS them, runs the scan as its pre-sweep and CLEARS dz_scan_src; so does every way out of the sequencer
+  // Channel from update_dz_d (fv3_dz.hip) to riem_solver3 (fv3_riem.hip), not a hint: update_dz_d under seq.dz_scan LEAVES the marched heights of the scan it
+  // left undone (null: none) and dz_min; riem_solver3 TAKES them and runs the scan as its pre-sweep (fv3_dz_scan_leave / fv3_dz_scan_take, fv3_ops.h: the only
+  // writer and the only reader); every way out of the sequencer clears dz_scan_src
   Real *dz_scan_src = nullptr;
   Real dz_scan_min = (Real)0;
   // Deferred accumulation of the Courant numbers (seq.acc_defer): crx, cry of every sub-step of a call, in arrays of their own (fields fxadv writes anyway)

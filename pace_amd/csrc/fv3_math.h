@@ -1,4 +1,4 @@
-// fv3_math.h -- range-specific fp64 log / exp for the SIM1 Riemann solvers (fv3_nh.hip).
+// fv3_math.h -- range-specific fp64 log / exp for the SIM1 Riemann solvers (fv3_riem.hip).
 //
 // Why: the solvers evaluate p = exp(gamma * log(rho R T)), dz ~ exp((kappa - 1) * log(p)), the layer-mean pressure
 // dp / log(p2 / p1) and pk = exp(kappa * log(p)) on every level: 7 calls per level in riem_solver3, 5 in riem_solver_c.  The

@@ -254,5 +254,19 @@ void nh_pgf_fused(fv3_ctx *c, fv3_stream_t s, const Real *pp, const Real *pk3, c
 int fv3_nh_p_grad_scaled(fv3_ctx *c, const fv3_field *u, const fv3_field *v, const fv3_field *pp, const fv3_field *gz, const fv3_field *pk3, const fv3_field *delp,
                          double dt, double ptop, double akap, double gz_scale, void *stream);
 int fv3_update_dz_c_from(fv3_ctx *c, const fv3_field *zs, const fv3_field *ut, const fv3_field *vt, const fv3_field *gz_in, const fv3_field *gz, const fv3_field *ws,
-                         double dt, void *stream);
+                         double dt, void *stream);  // (fv3_dz.hip)
+
+// The hand-off of update_dz_d's closing scan to riem_solver3 (fv3_ctx::dz_scan_src / dz_scan_min; decided by dz_scan_defers, fv3_col_plan.h).  update_dz_d
+// (fv3_dz.hip) LEAVES the marched heights and dz_min; riem_solver3 (fv3_riem.hip) TAKES them -- null: nothing was left -- and runs the scan as the pre-sweep
+// of its columns.  keep: frame pass 1, whose pass 2 takes them again for its own columns.  Every way out of the sequencer clears what nobody took.
+inline void fv3_dz_scan_leave(fv3_ctx *c, Real *heights, Real dz_min) {
+  c->dz_scan_src = heights;
+  c->dz_scan_min = dz_min;
+}
+inline Real *fv3_dz_scan_take(fv3_ctx *c, Real *dz_min, bool keep) {
+  Real *const heights = c->dz_scan_src;
+  *dz_min = c->dz_scan_min;
+  if (!keep) c->dz_scan_src = nullptr;
+  return heights;
+}
 

@@ -244,12 +244,12 @@ struct ProfParentScope {
 // What the sequencer tells the operators (fv3_seq_hints, one SeqScope per call; an operator called from anywhere else sees the defaults):
 //   hint                     set for                                          read by                        A/B switch
 //   csw_defer, uava_thin     c_sw (uava_thin: all but the last)               fv3_csw.hip                    FV3_CSW_DEFER=1 (off without), FV3_SEQ_UAVA=every
-//   frame_pass 1, 2          p_grad_c, riem_solver3, nh_p_grad + ray_fast     fv3_nh.hip                     FV3_FRAME_FIRST=0 / 1
+//   frame_pass 1, 2          p_grad_c, riem_solver3, nh_p_grad + ray_fast     fv3_nh.hip, fv3_riem.hip       FV3_FRAME_FIRST=0 / 1
 //   divgd_dead               d_sw, with the ping-pong                         fv3_dsw.hip                    FV3_SEQ_KEEP_DIVGD=1
 //   acc_first, heat_first    d_sw of the first sub-step                       fv3_dsw.hip                    FV3_ACC_STORE=0
 //   acc_defer, acc_sum_n     d_sw (acc_sum_n: the last)                       fv3_dsw.hip                    FV3_ACC_DEFER=0
-//   dz_scan                  update_dz_d                                      fv3_nh.hip                     FV3_DZ_SCAN=separate
-//   delz_dead                riem_solver3, all but the last                   fv3_nh.hip                     FV3_SEQ_DELZ=every
+//   dz_scan                  update_dz_d                                      fv3_dz.hip                     FV3_DZ_SCAN=separate
+//   delz_dead                riem_solver3, all but the last                   fv3_riem.hip                   FV3_SEQ_DELZ=every
 // The contract behind uava_thin, delz_dead and divgd_dead: BETWEEN the sub-steps of one call st->ua / st->va are complete only on the levels where d_sw reads
 // them (fv3_level_reads_uava, fv3_ops.h: the ONE predicate c_sw's store and d_sw's divergence kernel and level range share) and, on the other levels, in the
 // cells c_sw's boundary windows read; delz and the workspace's divgd are stale.  Nothing inside the sequencer reads them there.  All of them are final only
@@ -450,7 +450,7 @@ extern "C" int fv3_acoustic_step(fv3_ctx *c, const fv3_state *st, const fv3_work
                                                 &ws->pkc, &ws->pk3, &st->pk, &st->peln, &f_w[cur], stream));
       return FV3_OK;
     };
-    // (delz is read after the last sub-step of a call only: fv3_nh.hip, store_delz)
+    // (delz is read after the last sub-step of a call only: fv3_riem.hip, store_delz)
     TRY(feed_halos({.delz_dead = it < n_split - 1}, riem_solver3, [&]() -> int {
       HALO(FV3_HALO_ZH, 0);
       HALO(FV3_HALO_PKC, 0);
