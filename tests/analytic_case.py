@@ -29,7 +29,17 @@ and of tests/test_analytic_dynamics.py, on the same rotation with every damping 
 
 Edge lengths (pin 7) are great-circle distances of the corners (arc), never dx / dy.
 
-``python tests/analytic_case.py --record`` (``--record dynamics``: pins 6 - 9 alone, the other entries kept) measures the numpy oracle's error on the same inputs and writes tests/golden/analytic_pins.json;
+and of tests/test_analytic_damping.py (builders, exact solutions and checkers in tests/damping_case.py, which imports from here):
+
+  pin 10 c_sw         divgd == minus the divergence of rotation + potential flow at the corners                         (damping_case.DivergenceCase)
+  pin 11 c_sw, dt2!=0 delpc, ptc, omga at the departure points of the half step; the C-grid wind change against the tendency (damping_case.CswCase)
+  pin 12 d_sw         the divergence damping, on against off, against the closed-form damping field                     (damping_case.DivDampCase)
+  pin 13 d_sw at rest the del-n chains of delp, pt, q_con, w and the vorticity on a harmonic, per level of the sponge   (damping_case.RestCase)
+  pin 14 damping heat d_sw's heat_source == the kinetic energy the one-pass damping takes; del2_cubed on a harmonic; apply_diffusive_heating
+                      pointwise against the gas law                                                                     (damping_case.heat_errors, Del2Case, heating_case)
+  pin 15 convergence  second order from C24 to C48 wherever the oracle's record shows it: pins 10 and 12 away from the tile edges, pins 13 and 14 at the tile centres
+
+``python tests/analytic_case.py --record`` (``--record dynamics``: pins 6 - 9 alone, ``--record damping``: pins 10 - 14 alone, the other entries kept) measures the numpy oracle's error on the same inputs and writes tests/golden/analytic_pins.json;
 the tests hold the library to 1.5 x those figures and to the second-order ratio between C24 and C48 (check_convergence).
 """
 import json
@@ -1085,13 +1095,23 @@ def record(path=GOLDEN):
     out["pin5a"] = {"K": measure_pgf_k()}
     print("pin5a", out["pin5a"])
     out.update(measure_dynamics())
-    return write(out, path)
+    write(out, path)
+    return record_damping(path)
 
 
 def record_dynamics(path=GOLDEN):
     """pins 6 - 9 alone, into the file as it stands (``--record dynamics``)"""
     out = recorded()
     out.update(measure_dynamics())
+    return write(out, path)
+
+
+def record_damping(path=GOLDEN):
+    """pins 10, 12 and 13 (tests/damping_case.py) alone, into the file as it stands (``--record damping``)"""
+    import damping_case
+
+    out = recorded()
+    out.update(damping_case.measure_damping())
     return write(out, path)
 
 
@@ -1113,6 +1133,6 @@ if __name__ == "__main__":
         if p not in sys.path:
             sys.path.insert(0, p)
     if "--record" in sys.argv:
-        record_dynamics() if "dynamics" in sys.argv else record()
+        record_dynamics() if "dynamics" in sys.argv else record_damping() if "damping" in sys.argv else record()
     else:
         print(__doc__)

@@ -418,8 +418,10 @@ def test_remap_keeps_profiles_linear_in_pressure(backend, nz):
 # the recorded figures, and the controls: every checker has teeth (CPU, oracle only)
 # ---------------------------------------------------------------------------------------------------------------------------
 def test_recorded_oracle_figures_are_fresh():
-    """the C24 entries of pins 1, 3 and 4, and of pins 6, 7 and 9 (tests/test_analytic_dynamics.py), re-measured with the oracle: within 1 % of
-    tests/golden/analytic_pins.json (figures that are round-off, below 1e-12, are not compared)"""
+    """the C24 entries of pins 1, 3 and 4, of pins 6, 7 and 9 (tests/test_analytic_dynamics.py) and of pins 10 - 13 (tests/test_analytic_damping.py),
+    re-measured with the oracle: within 1 % of tests/golden/analytic_pins.json (figures that are round-off, below 1e-12, are not compared)"""
+    import damping_case
+
     now = ac.measure_single_call_pins("c24")
     now.update(ac.measure_d_sw("c24"))
     now["pin9"] = ac.measure_heights("c24")
@@ -429,6 +431,8 @@ def test_recorded_oracle_figures_are_fresh():
             if max(abs(v), abs(want)) < 1e-12:
                 continue
             assert abs(v - want) <= 0.01 * abs(want), f"{pin} c24 {k}: {v} now, {want} recorded -- run python tests/analytic_case.py --record"
+    stale = damping_case.stale_entries(REC)
+    assert not stale, f"{stale} -- run python tests/analytic_case.py --record damping"
 
 
 def _oracle_pin(shape, pin, spoil):
