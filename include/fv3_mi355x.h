@@ -593,6 +593,43 @@ int fv3_remap_moist_sat(fv3_ctx *, int n_tracers, const fv3_field *const *tracer
 int fv3_cubed_to_latlon(fv3_ctx *, int order, const fv3_field *u, const fv3_field *v, const fv3_field *ua, const fv3_field *va,
                         const fv3_field *a11, const fv3_field *a12, const fv3_field *a21, const fv3_field *a22, void *stream);
 
+/* ---- physics coupling: a source of tendencies (fv3_hs.hip) and their application to the D-grid state (fv3_updphys.hip) ----------
+ *
+ * Held-Suarez (1994) forcing [Held & Suarez, Bull. Amer. Meteor. Soc. 75, 1825-1830]; the defaults of the paper are
+ * sigma_b = 0.7, k_f = 1 / 86400 1/s, k_a = 1 / (40 * 86400), k_s = 1 / (4 * 86400), delta_t_y = 60 K, delta_theta_z = 10 K,
+ * p0 = 1e5 Pa, kappa = 2 / 7, t_min = 200 K. */
+typedef struct fv3_held_suarez {
+  double sigma_b, k_f, k_a, k_s, delta_t_y, delta_theta_z, p0, kappa, t_min;
+} fv3_held_suarez;
+
+/* fv3_held_suarez_tend: u_dt, v_dt, t_dt on the compute cells of levels 0 .. nz-1 from ua, va (eastward / northward cell-centre
+ * winds), pt (temperature, K), delp (Pa) and lat (2-D field, radians).  Stateless: pe(0) = ptop, pe(k+1) = pe(k) + delp(k),
+ * ps = pe(nz), p = (pe(k) + pe(k+1)) / 2, sigma = p / ps;
+ *   s = max(0, (sigma - sigma_b) / (1 - sigma_b)),  k_v = k_f s,  k_T = k_a + (k_s - k_a) s cos^4(lat),
+ *   T_eq = max(t_min, (315 - delta_t_y sin^2(lat) - delta_theta_z ln(p / p0) cos^2(lat)) (p / p0)^kappa),
+ *   u_dt = -k_v / (1 + dt k_v) ua, v_dt likewise from va, t_dt = -k_T / (1 + dt k_T) (pt - T_eq)   (implicit in dt; dt = 0: explicit).
+ * Nothing outside the compute cells of the outputs is written, no input is written.  FV3_ERR_ARG: an output that aliases an
+ * input or another output, dt < 0 or not finite, parameters outside 0 <= sigma_b < 1, p0 > 0, k_* >= 0. */
+int fv3_held_suarez_tend(fv3_ctx *, const fv3_held_suarez *params, const fv3_field *ua, const fv3_field *va, const fv3_field *pt,
+                         const fv3_field *delp, const fv3_field *lat, const fv3_field *u_dt, const fv3_field *v_dt, const fv3_field *t_dt,
+                         double ptop, double dt, void *stream);
+
+/* fv3_apply_tendencies (FV3 fv_update_phys: the temperature update and update_dwinds_phys; pyFV3 ApplyPhysicsToDycore):
+ *   pt += dt t_dt on the compute cells;  with V = u_dt vlon + v_dt vlat (Cartesian tendency at a cell centre)
+ *   u(i,j) += dt (V(i,j-1) + V(i,j)) / 2 . es(i,j)  for i = 1..nx, j = 1..ny+1,
+ *   v(i,j) += dt (V(i-1,j) + V(i,j)) / 2 . ew(i,j)  for i = 1..nx+1, j = 1..ny,
+ * on a tile-edge face with the averaged vector interpolated along the edge, (1 - w) Vbar_f + w Vbar_f' (f' = the neighbouring
+ * face towards the middle of the edge).  2-D fields (GridData of the same names): vlon_x, vlon_y / vlat_x .. vlat_z the east /
+ * north unit vectors of the cell centres, es_* / ew_* the unit tangents of the x- / y-faces, ev_um / ev_up (ev_vm / ev_vp) the
+ * weight w of a south / north (west / east) tile-edge face whose f' has index - 1 / + 1, zero on every other face.  The caller
+ * updates one halo cell of u_dt, v_dt (as scalars: the components are geographic) before the call; cube-corner halo cells are not
+ * read.  Levels 0 .. nz-1.  FV3_ERR_ARG: a tendency that aliases u / v / pt, dt not finite. */
+int fv3_apply_tendencies(fv3_ctx *, const fv3_field *u, const fv3_field *v, const fv3_field *pt, const fv3_field *u_dt, const fv3_field *v_dt,
+                         const fv3_field *t_dt, const fv3_field *vlon_x, const fv3_field *vlon_y, const fv3_field *vlat_x,
+                         const fv3_field *vlat_y, const fv3_field *vlat_z, const fv3_field *es_x, const fv3_field *es_y, const fv3_field *es_z,
+                         const fv3_field *ew_x, const fv3_field *ew_y, const fv3_field *ew_z, const fv3_field *ev_um, const fv3_field *ev_up,
+                         const fv3_field *ev_vm, const fv3_field *ev_vp, double dt, void *stream);
+
 /* ---- driver diagnostics (fv3_diag.hip): what the driver stores every output_frequency steps ------------------------------
  * [REF driver/pace/driver/diagnostics.py].  Neither entry allocates: the caller owns `out`, a contiguous device array in the
  * build's Real.  Neither reads a halo cell or the pad level.

@@ -13,7 +13,9 @@ the vertical filling of negative tracer values at the end of the remap with ``dy
 ``--moist``) FV3's ``neg_adj3`` fixes negative water species after the conversion back to temperature and the start-up line and the json
 say ``"neg_adj": true`` (otherwise ``false``); with ``--moist`` and ``do_sat_adj: true`` in the yaml (or ``--sat-adj on``; ``--sat-adj off``
 overrides the yaml) FV3's saturation adjustment runs inside every remap with the yaml's ``tau_*`` / ``ql_gen`` ... keys
-(``pace_amd.stencils.SatAdjustConfig``) and the start-up line and the json say ``"sat_adj": true`` (otherwise ``false``) -- and writes
+(``pace_amd.stencils.SatAdjustConfig``) and the start-up line and the json say ``"sat_adj": true`` (otherwise ``false``); with ``--held-suarez``
+(needs ``--temperature --remap --latlon-winds``) every step ends with the Held-Suarez forcing and ``ApplyPhysicsToDycore`` and the start-up line and
+the json say ``"forcing": "held_suarez"`` (otherwise ``"none"``) -- and writes
 the per-step times in the layout the reference's performance collector uses
 (``{"times": {<timer>: {"hits": n, "times": [[...per step...] per rank]}}}``, timers ``mainloop``, ``DynCore``,
 ``TracerAdvection``, ``Remapping`` [REF tests/main/driver/test_driver.py:77-121]).  With ``--tracers N --remap`` the step is the
@@ -196,6 +198,9 @@ def main(argv=None):
     ap.add_argument("--sat-adj", choices=("yaml", "on", "off"), default="yaml",
                     help="saturation adjustment (FV3 fv_sat_adj) inside every remap (needs --moist): yaml = dycore_config.do_sat_adj (absent: off) with the yaml's tau_* / ql_gen ... keys; "
                          "on / off override it")
+    ap.add_argument("--held-suarez", action="store_true",
+                    help="end every step with the Held-Suarez (1994) forcing and ApplyPhysicsToDycore (needs --temperature --remap --latlon-winds): Newtonian relaxation of the "
+                         "temperature and Rayleigh friction on the low-level winds, applied to the D-grid state with dt_atmos")
     ap.add_argument("--diagnostics-path", default=None, help="directory of the diagnostics (overrides diagnostics_config.path of the yaml)")
     ap.add_argument("--no-diagnostics", action="store_true", help="ignore the yaml's diagnostics_config block")
     a = ap.parse_args(argv)
@@ -203,6 +208,8 @@ def main(argv=None):
         sys.exit("--temperature needs --remap: the conversion back to temperature is the last step of the remap")
     if a.moist and not (a.temperature and a.remap):
         sys.exit("--moist needs --temperature --remap: moist_cv sits in the preamble and the remap of DynamicalCore.step_dynamics")
+    if a.held_suarez and not (a.temperature and a.remap and a.latlon_winds):
+        sys.exit("--held-suarez needs --temperature --remap --latlon-winds: the forcing reads the temperature and the eastward / northward winds of the step's end state")
     if a.neg_adj and not a.moist:
         sys.exit("--neg-adj needs --moist: neg_adj3 works on the six water species of the moist step")
     if a.sat_adj == "on" and not a.moist:
@@ -250,6 +257,9 @@ def main(argv=None):
     say(f'"sat_adj": {str(sat_adj).lower()}' + ("" if a.sat_adj == "yaml" else f" (--sat-adj {a.sat_adj})")
         + ("  (fv_sat_adj on the six water species inside every remap, between the fill and moist_cv)" if sat_adj
            else "  (no phase changes; --moist with do_sat_adj: true in the yaml or --sat-adj on: fv_sat_adj inside every remap)"))
+    forcing = "held_suarez" if a.held_suarez else "none"
+    say(f'"forcing": "{forcing}"' + ("  (Held-Suarez tendencies from the step's end state, applied to u, v, pt by ApplyPhysicsToDycore with dt_atmos)" if a.held_suarez
+                                     else "  (an unforced initial-value problem; --held-suarez with --temperature --remap --latlon-winds: Held-Suarez forcing)"))
     say(f'"grid": {json.dumps(grid_entry(run["grid"]))}' + ("  (Schmidt transform of the generated corner positions; divergence damping in its stretched form)" if grid_entry(run["grid"]) != "uniform"
                                                             else "  (grid_config.config.stretch_factor / lon_target / lat_target: a grid refined about a target point)"))
     if run["init"] == "analytic" and str(run["case"]).startswith("baroclinic"):
@@ -273,7 +283,7 @@ def main(argv=None):
     kw = {k: dy[k] for k in ("k_split", "n_split") if k in dy}
     h = DycoreHarness(nx_tile=run["nx_tile"], nz=run["nz"], layout=run["layout"], dt_atmos=run["dt_atmos"], world_size=world, proc=rank,
                       device=f"cuda:{local_rank}", dtype=dtype, verbose=(rank == 0), init=init, config_overrides={k: v for k, v in dy.items() if k not in ("k_split", "n_split", "fill")},
-                      n_tracers=a.tracers, hord_tr=int(dy.get("hord_tr", 8)), remap=a.remap, fill=fill, latlon_winds=a.latlon_winds, temperature=a.temperature, moist=a.moist, neg_adj=a.neg_adj, sat_adj=sat_adj, sat_adjust_config=sat_cfg, **harness_grid_kwargs(run["grid"]), **kw)
+                      n_tracers=a.tracers, hord_tr=int(dy.get("hord_tr", 8)), remap=a.remap, fill=fill, latlon_winds=a.latlon_winds, temperature=a.temperature, moist=a.moist, neg_adj=a.neg_adj, sat_adj=sat_adj, sat_adjust_config=sat_cfg, held_suarez=a.held_suarez, **harness_grid_kwargs(run["grid"]), **kw)
     if run["device_sync"]:
         h.sf.set_device_sync(True)
     if a.restart:
@@ -361,7 +371,7 @@ def main(argv=None):
         sdpd = run["dt_atmos"] / mean
         out = a.out or f"{run['experiment']}_fv3_mi355x.json"
         json.dump({"setup": {"experiment": run["experiment"], "nx_tile": run["nx_tile"], "nz": run["nz"], "layout": list(run["layout"]), "dt_atmos": run["dt_atmos"],
-                             "k_split": h.cfg.k_split, "n_split": h.cfg.n_split, "n_gpus": world, "backend": "hip:gfx950", "dycore_only": True, "acoustic_only": not (a.tracers or a.remap), "tracers": a.tracers, "remap": bool(a.remap), "fill": fill, "pt": pt_form, "thermodynamics": thermo, "neg_adj": bool(a.neg_adj), "sat_adj": sat_adj, "grid": grid_entry(run["grid"]), "finite": ok,
+                             "k_split": h.cfg.k_split, "n_split": h.cfg.n_split, "n_gpus": world, "backend": "hip:gfx950", "dycore_only": True, "acoustic_only": not (a.tracers or a.remap), "tracers": a.tracers, "remap": bool(a.remap), "fill": fill, "pt": pt_form, "thermodynamics": thermo, "neg_adj": bool(a.neg_adj), "sat_adj": sat_adj, "forcing": forcing, "grid": grid_entry(run["grid"]), "finite": ok,
                              "note": ("a step here is k_split AcousticDynamics calls; the reference's dycore_only mainloop (DynamicalCore.step_dynamics) also runs tracer "
                                       "advection and the Lagrangian-to-Eulerian remap (--tracers N --remap add them): not comparable with the reference's 'mainloop' timer")
                              if not (a.tracers and a.remap) else

@@ -21,7 +21,8 @@ the six water species by FV3's ``moist_cv`` where FV3 derives them: step 1 becom
 (``fv3_remap_moist``: remap, fill, ``q_con`` / ``cappa`` from the remapped and filled species, ``pkz`` with the new ``cappa``); step 3 is
 unchanged and reads the ``q_con`` the last remap wrote.  With ``saturation_adjustment`` every remap of step 2 is the adjusting one
 (``fv3_remap_moist_sat``: FV3's ``fv_sat_adj`` between the fill and ``moist_cv``, with ``mdt = timestep / k_split`` and its second pass
-to full saturation in the last remap of the step).  The energy fixer and the physics coupling are outside this build.  Every buffer (``dp1``, ``ps``, the operators' own) is allocated by the
+to full saturation in the last remap of the step).  The energy fixer is outside this build; the physics coupling is the caller's second call after the step
+(:class:`~pace_amd.stencils.ApplyPhysicsToDycore`, which ``DycoreHarness(held_suarez=True)`` runs with the Held-Suarez forcing).  Every buffer (``dp1``, ``ps``, the operators' own) is allocated by the
 constructor; ``step_dynamics`` allocates nothing.
 """
 from __future__ import annotations

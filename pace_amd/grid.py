@@ -316,6 +316,72 @@ def _pad(a, shape):
     return out
 
 
+UPDPHYS_FIELDS = "vlon_x vlon_y vlat_x vlat_y vlat_z es_x es_y es_z ew_x ew_y ew_z ev_um ev_up ev_vm ev_vp".split()
+
+
+def _edge_vect(c1, c2, pa, pb, g, n):
+    """The tile-edge weights of ``update_dwinds_phys`` (FV3's ``edge_vect_*``) for the faces of one tile edge held in one row / column
+    of the storage.  ``c1, c2[m, 3]``: the two cell centres that straddle face m (one of them across the edge, at its true
+    position), ``pa, pb[m, 3]``: the face's end points, ``g[m]``: the face's tile-global index (0-based; faces outside
+    ``[0, n)`` lie in cube-corner blocks and get no weight).
+
+    The great circle through the two centres crosses the edge at ``x_f``: there the mean of the two centre vectors is second-order
+    accurate.  The D-grid wind sits at the face mid-point ``m_f``; ``w_f`` is the signed fraction of the chord ``x_f -> x_f'`` at which
+    ``m_f`` projects, ``f'`` being the neighbouring face towards the middle of the edge (``g + 1`` for ``g < n // 2``, else
+    ``g - 1``).  Returns ``(wm, wp)``: the weight where the neighbour is ``g - 1`` / ``g + 1``, zero elsewhere."""
+    m = len(g)
+    wm, wp = np.zeros(m), np.zeros(m)
+    ok = (g >= 0) & (g < n)
+    if n < 2 or not ok.any():
+        return wm, wp
+    idx = np.nonzero(ok)[0]
+    mid = _mid(pa[idx], pb[idx])
+    x = _normalize(np.cross(np.cross(c1[idx], c2[idx]), np.cross(pa[idx], pb[idx])))
+    x = x * np.where(np.sum(x * mid, -1, keepdims=True) < 0.0, -1.0, 1.0)  # (of the two antipodal crossings the one on the face)
+    pos = {int(i): r for r, i in enumerate(idx)}
+    for r, i in enumerate(idx):
+        step = 1 if g[i] < n // 2 else -1
+        o = pos.get(int(i) + step)
+        if o is None:  # the neighbour lies outside the stored row: the face is not one this rank updates
+            continue
+        d = x[o] - x[r]
+        w = float(np.dot(mid[r] - x[r], d) / np.dot(d, d))
+        if step > 0:
+            wp[i] = w
+        else:
+            wm[i] = w
+    return wm, wp
+
+
+def _updphys_terms(P, A, vlon, vlat, x0, y0, n, nx, ny, nh, flags) -> Dict[str, np.ndarray]:
+    """Metric terms of ``ApplyPhysicsToDycore`` (FV3 ``update_dwinds_phys``), from corner and centre positions alone: the east / north
+    unit vectors of the cell centres (halo cells at their true positions; ``vlon`` has no z component), the unit tangents ``es`` /
+    ``ew`` of the x-faces (where ``u`` lives) / y-faces (``v``) at their mid-points, and the tile-edge weights ``ev_u*`` (faces of the
+    south / north tile edge) and ``ev_v*`` (west / east), ``*m`` / ``*p`` for a neighbour at index - 1 / + 1 (:func:`_edge_vect`)."""
+    out = {"vlon_x": vlon[..., 0], "vlon_y": vlon[..., 1], "vlat_x": vlat[..., 0], "vlat_y": vlat[..., 1], "vlat_z": vlat[..., 2]}
+    es = _normalize(P[1:, :] - P[:-1, :])  # (nI-1, nJ): the chord of an arc is tangent to the sphere at the arc's mid-point
+    ew = _normalize(P[:, 1:] - P[:, :-1])  # (nI, nJ-1)
+    for k in range(3):
+        out["es_" + "xyz"[k]] = es[..., k]
+        out["ew_" + "xyz"[k]] = ew[..., k]
+    ev_um, ev_up = np.zeros(es.shape[:2]), np.zeros(es.shape[:2])
+    ev_vm, ev_vp = np.zeros(ew.shape[:2]), np.zeros(ew.shape[:2])
+    gi = x0 + np.arange(es.shape[0]) - nh
+    gj = y0 + np.arange(ew.shape[1]) - nh
+    own_i = slice(nh, nh + nx)
+    own_j = slice(nh, nh + ny)
+    for has, jj in ((flags["south"], nh), (flags["north"], nh + ny)):
+        if has:
+            wm, wp = _edge_vect(A[:, jj - 1], A[:, jj], P[:-1, jj], P[1:, jj], gi, n)
+            ev_um[own_i, jj], ev_up[own_i, jj] = wm[own_i], wp[own_i]
+    for has, ii in ((flags["west"], nh), (flags["east"], nh + nx)):
+        if has:
+            wm, wp = _edge_vect(A[ii - 1, :], A[ii, :], P[ii, :-1], P[ii, 1:], gj, n)
+            ev_vm[ii, own_j], ev_vp[ii, own_j] = wm[own_j], wp[own_j]
+    out.update(ev_um=ev_um, ev_up=ev_up, ev_vm=ev_vm, ev_vp=ev_vp)
+    return out
+
+
 def make_grid(
     part: CubedSpherePartitioner,
     rank: int,
@@ -542,6 +608,8 @@ def make_grid(
     put("sin_sg5", sin[5])  # cell centre (tracer_2d_1l's Courant-number bound)
     for k, a in c2l.items():
         put(k, a)  # CubedToLatLon
+    for k, a in _updphys_terms(P, A, vlon, vlat, x0, y0, n, nx, ny, nh, flags).items():
+        put(k, a)  # ApplyPhysicsToDycore
     put("fC", fC), put("f0", f0)
     put("del6_u", del6_u), put("del6_v", del6_v), put("divg_u", divg_u), put("divg_v", divg_v)
     put("lon", lon_c), put("lat", lat_c), put("lon_agrid", lon_a), put("lat_agrid", lat_a)

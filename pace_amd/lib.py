@@ -126,6 +126,13 @@ class fv3_sat_params(C.Structure):
     _fields_ = [(n, C.c_double) for n in SAT_PARAMS]
 
 
+HS_PARAMS = "sigma_b k_f k_a k_s delta_t_y delta_theta_z p0 kappa t_min".split()
+
+
+class fv3_held_suarez(C.Structure):
+    _fields_ = [(n, C.c_double) for n in HS_PARAMS]
+
+
 _D = C.c_double
 _I = C.c_int
 _S = C.c_void_p  # stream
@@ -195,6 +202,8 @@ _PROTOS = {
     "fv3_sat_adj_tables": (C.c_int, [C.c_void_p, P(C.c_double), C.c_long]),
     "fv3_remap_moist_sat": (C.c_int, [C.c_void_p, _I, P(F)] + [F] * 14 + [P(fv3_water), _I, P(fv3_latent), P(fv3_sat_params), _D, _I, _S]),
     "fv3_cubed_to_latlon": (C.c_int, [C.c_void_p, _I] + [F] * 8 + [_S]),
+    "fv3_held_suarez_tend": (C.c_int, [C.c_void_p, P(fv3_held_suarez)] + [F] * 8 + [_D, _D, _S]),
+    "fv3_apply_tendencies": (C.c_int, [C.c_void_p] + [F] * 21 + [_D, _S]),
     "fv3_diag_pack": (C.c_int, [C.c_void_p, F, _I, _I, _I, _I, C.c_void_p, C.c_long, _S]),
     "fv3_diag_column_integral": (C.c_int, [C.c_void_p, F, F, C.c_void_p, C.c_long, _S]),
 }

@@ -603,6 +603,111 @@ class CubedToLatLon(_Op):
         self.sf.call("cubed_to_latlon", self.order, u.fref, v.fref, ua.fref, va.fref, self.a11.fref, self.a12.fref, self.a21.fref, self.a22.fref)
 
 
+@dataclasses.dataclass
+class HeldSuarezConfig:
+    """The constants of the Held-Suarez (1994) forcing (``fv3_held_suarez`` in include/fv3_mi355x.h); the defaults are the paper's:
+    ``sigma_b`` the top of the boundary layer in sigma, ``k_f`` the friction rate at the surface (1/s), ``k_a`` / ``k_s`` the relaxation
+    rates of the free atmosphere / at the surface on the equator (1/s), ``delta_t_y`` the equator-to-pole difference (K),
+    ``delta_theta_z`` the static-stability parameter (K), ``p0`` the reference pressure (Pa), ``kappa = R / cp``, ``t_min`` the floor
+    of the equilibrium temperature (K)."""
+
+    sigma_b: float = 0.7
+    k_f: float = 1.0 / 86400.0
+    k_a: float = 1.0 / (40.0 * 86400.0)
+    k_s: float = 1.0 / (4.0 * 86400.0)
+    delta_t_y: float = 60.0
+    delta_theta_z: float = 10.0
+    p0: float = 1.0e5
+    kappa: float = 2.0 / 7.0
+    t_min: float = 200.0
+
+    def validate(self):
+        if not 0.0 <= self.sigma_b < 1.0:
+            raise ValueError(f"HeldSuarezConfig: sigma_b = {self.sigma_b} (0 <= sigma_b < 1)")
+        if not self.p0 > 0.0:
+            raise ValueError(f"HeldSuarezConfig: p0 = {self.p0} (a pressure in Pa)")
+        for n in ("k_f", "k_a", "k_s"):
+            if not getattr(self, n) >= 0.0:
+                raise ValueError(f"HeldSuarezConfig: {n} = {getattr(self, n)} (a rate in 1/s, >= 0)")
+        return self
+
+
+class HeldSuarezForcing(_Op):
+    """The Held-Suarez (1994) forcing as cell-centre tendencies (``fv3_held_suarez_tend`` in include/fv3_mi355x.h holds the formulas):
+    Rayleigh friction on the eastward / northward winds ``ua``, ``va`` below ``sigma_b`` and Newtonian relaxation of the temperature
+    ``pt`` (K) to the paper's equilibrium, in the implicit form ``-k / (1 + dt k)``.  Call as
+    ``(ua, va, pt, delp, u_dt, v_dt, pt_dt, dt, ptop=None)``: the three tendencies are written on the compute cells, nothing else is
+    touched; ``ptop`` defaults to the grid's.  The operator is stateless: the pressure is formed from ``ptop`` and ``delp``."""
+
+    def __init__(self, stencil_factory, quantity_factory=None, grid_data=None, config: Optional[HeldSuarezConfig] = None):
+        import ctypes as C
+
+        from . import lib as _lib
+
+        super().__init__(stencil_factory, quantity_factory, grid_data)
+        self.config = (config or HeldSuarezConfig()).validate()
+        self.params = _lib.fv3_held_suarez(*[float(getattr(self.config, n)) for n in _lib.HS_PARAMS])
+        self._pref = C.byref(self.params)
+        self.lat = self.qf.from_array([g.fields["lat_agrid"] for g in self.sf.grids], ("x", "y"))
+        self.ptop = float(self.sf.grids[0].ptop)
+
+    def __call__(self, ua, va, pt, delp, u_dt, v_dt, pt_dt, dt, ptop=None):
+        self.sf.call("held_suarez_tend", self._pref, ua.fref, va.fref, pt.fref, delp.fref, self.lat.fref, u_dt.fref, v_dt.fref, pt_dt.fref,
+                     float(self.ptop if ptop is None else ptop), float(dt))
+
+
+class ApplyPhysicsToDycore(_Op):
+    """Cell-centre tendencies applied to the D-grid state (FV3 ``fv_update_phys``; pyFV3's ``ApplyPhysicsToDycore``): call as the
+    reference's ``(state, u_dt, v_dt, pt_dt, dt)`` with ``u_dt``, ``v_dt`` the eastward / northward wind tendencies (m/s^2) and
+    ``pt_dt`` the temperature tendency (K/s) on the compute cells.  ``state.pt += dt * pt_dt``: ``pt`` is the temperature in K, so the
+    call belongs after ``DynamicalCore.step_dynamics``; the ``cp / cvm`` scaling that turns a heating at constant pressure into the
+    tendency of this model's temperature is the caller's.  The wind tendencies go to the D-grid faces the rank updates
+    (``update_dwinds_phys``, ``fv3_apply_tendencies`` in include/fv3_mi355x.h holds the form, tile-edge interpolation included); the
+    call starts with a one-cell halo update of ``u_dt``, ``v_dt`` -- geographic components, exchanged as two scalars (``comm``: a
+    :class:`pace_amd.halo.Layout`, None = every rank in this process).
+
+    Not built, and refused where they can be asked for: tracer tendencies, the moist ``delp`` adjustment, nudging, the dry
+    convective adjustment."""
+
+    def __init__(self, stencil_factory, quantity_factory=None, grid_data=None, comm=None, *, tracer_tendencies=None, nudge=False, do_sg_conv=False):
+        from .grid import UPDPHYS_FIELDS
+
+        super().__init__(stencil_factory, quantity_factory, grid_data)
+        if tracer_tendencies:
+            raise NotImplementedError("ApplyPhysicsToDycore: tracer tendencies (and the delp adjustment that goes with them) are not built")
+        if nudge:
+            raise NotImplementedError("ApplyPhysicsToDycore: nudging is not built")
+        if do_sg_conv:
+            raise NotImplementedError("ApplyPhysicsToDycore: the dry convective adjustment (fv_subgridz) is not built")
+        missing = [n for n in UPDPHYS_FIELDS if n not in self.sf.grids[0].fields]
+        if missing:
+            raise ValueError(f"ApplyPhysicsToDycore: the grid data lacks {', '.join(missing)} (pace_amd.grid.make_grid forms them)")
+        self.comm = comm
+        # the metric terms of the context's sub-domains, uploaded once (2-D fields like phis)
+        self.metrics = [self.qf.from_array([g.fields[n] for g in self.sf.grids], ("x", "y")) for n in UPDPHYS_FIELDS]
+        self._updater = None
+        self._bound = None
+
+    def _tendency_updater(self, u_dt, v_dt):
+        from .halo import HaloExchanger, Layout
+        from .topology import CubedSpherePartitioner
+
+        key = (id(u_dt), id(v_dt))
+        if self._bound != key:
+            lay = self.comm
+            if lay is None:
+                cfg = self.sf.config
+                lay = Layout(CubedSpherePartitioner(cfg.npx - 1, tuple(cfg.layout)), 1, 0)
+            ex = HaloExchanger.shared(self.sf, lay, group=getattr(lay, "group", None))
+            self._updater = ex.updater("cell", [(u_dt,), (v_dt,)], n_halo=1)
+            self._bound = key
+        return self._updater
+
+    def __call__(self, state, u_dt, v_dt, pt_dt, dt):
+        self._tendency_updater(u_dt, v_dt).update()
+        self.sf.call("apply_tendencies", state.u.fref, state.v.fref, state.pt.fref, u_dt.fref, v_dt.fref, pt_dt.fref, *[m.fref for m in self.metrics], float(dt))
+
+
 def _box_extent(sf, q: Quantity, op: str):
     """(ni, nj, nk) of the compute box of ``q`` from its dims: ``x_interface`` / ``y_interface`` / ``z_interface`` add one; nk is
     None for a 2-D quantity."""
