@@ -17,6 +17,7 @@ grid about the target with a Schmidt transform (``pace_amd.grid.SchmidtTransform
 ``held_suarez`` (needs ``temperature``, ``remap`` and ``latlon_winds``; ``held_suarez_config``: a ``pace_amd.stencils.HeldSuarezConfig``) adds the
 second half of the reference driver's step [REF driver/pace/driver/driver.py:494-530]: after ``step_dynamics`` the Held-Suarez forcing forms
 ``u_dt``, ``v_dt``, ``pt_dt`` from the end state and ``ApplyPhysicsToDycore`` applies them with ``dt_atmos`` (timer clocks "HeldSuarez", "ApplyPhysics").
+``constants`` (a ``pace_amd.constants.ConstantSet``; None: the project's): the constants the grids and the kernels are made with, e.g. ``OMEGA = 0`` for a planet that does not turn.
 """
 from __future__ import annotations
 
@@ -93,6 +94,7 @@ class DycoreHarness:
         lat_target: float = -90.0,
         held_suarez: bool = False,
         held_suarez_config=None,
+        constants=None,
         _testing_token=None,
     ):
         if held_suarez and not (temperature and remap and latlon_winds):
@@ -117,7 +119,7 @@ class DycoreHarness:
             vapor = "qvapor"
             n_tracers = max(int(n_tracers), len(WATER_NAMES))
         self.moist = bool(moist)
-        self.c = get_constants()
+        self.c = constants or get_constants()  # (constants: another ConstantSet for the grids and the kernels, e.g. a planet that does not turn)
         self.part = CubedSpherePartitioner(nx_tile, tuple(layout))
         # a stretch factor other than 1 gives the Schmidt-transformed grid AND the stretched form of the divergence damping
         # (the two are separate inputs below this class: make_grid's stretch, the config's stretched_grid)
@@ -129,7 +131,7 @@ class DycoreHarness:
         self.layout.group = group
         self.layout.loopback = bool(loopback)  # this process plays `proc` of `world_size` alone, its messages looped back (timing runs)
         t0 = time.time()
-        self.grids = [make_grid(self.part, r, nz=nz, ak=ak, bk=bk, stretch=self.stretch) for r in self.layout.local_ranks]
+        self.grids = [make_grid(self.part, r, nz=nz, ak=ak, bk=bk, stretch=self.stretch, constants=self.c) for r in self.layout.local_ranks]
         if verbose:
             print(f"[harness] grid for ranks {self.layout.local_ranks} in {time.time() - t0:.1f}s", flush=True)
         self.sf = StencilFactory(self.grids, self.cfg, self.c, backend=backend, device=device, dtype=dtype, _testing_token=_testing_token)

@@ -39,7 +39,14 @@ and of tests/test_analytic_damping.py (builders, exact solutions and checkers in
                       pointwise against the gas law                                                                     (damping_case.heat_errors, Del2Case, heating_case)
   pin 15 convergence  second order from C24 to C48 wherever the oracle's record shows it: pins 10 and 12 away from the tile edges, pins 13 and 14 at the tile centres
 
-``python tests/analytic_case.py --record`` (``--record dynamics``: pins 6 - 9 alone, ``--record damping``: pins 10 - 14 alone, the other entries kept) measures the numpy oracle's error on the same inputs and writes tests/golden/analytic_pins.json;
+and of tests/test_analytic_steady.py (builders, exact solutions and checkers in tests/steady_case.py, which imports from here):
+
+  pin 16 one acoustic call      isothermal solid-body rotation in gradient-wind balance keeps every prognostic field                     (steady_case.SteadyCase.tendencies)
+  pin 17 the call's accumulators  mfxd, mfyd == n_split delp x the exact swept area; cxd, cyd x the upwind area == n_split x the swept area  (steady_case.SteadyCase.accumulator_errors)
+  pin 18 step_dynamics          two model steps with remap, tracers, temperature bookends and latlon winds return the closed-form state  (steady_case.StepCase)
+  pin 19 rest over terrain      three acoustic calls leave the isothermal atmosphere at rest over a 3 km mountain at rest                (steady_case.SteadyCase.rest_figures)
+
+``python tests/analytic_case.py --record`` (``--record dynamics``: pins 6 - 9 alone, ``--record damping``: pins 10 - 14 alone, ``--record steady``: pins 16 - 19 alone, the other entries kept) measures the numpy oracle's error on the same inputs and writes tests/golden/analytic_pins.json;
 the tests hold the library to 1.5 x those figures and to the second-order ratio between C24 and C48 (check_convergence).
 """
 import json
@@ -1115,6 +1122,15 @@ def record_damping(path=GOLDEN):
     return write(out, path)
 
 
+def record_steady(path=GOLDEN):
+    """pins 16 - 19 (tests/steady_case.py) alone, into the file as it stands (``--record steady``)"""
+    import steady_case
+
+    out = recorded()
+    out.update(steady_case.measure_steady())
+    return write(out, path)
+
+
 def write(out, path):
     with open(path, "w") as f:
         json.dump(out, f, indent=1, sort_keys=True)
@@ -1133,6 +1149,6 @@ if __name__ == "__main__":
         if p not in sys.path:
             sys.path.insert(0, p)
     if "--record" in sys.argv:
-        record_dynamics() if "dynamics" in sys.argv else record_damping() if "damping" in sys.argv else record()
+        record_dynamics() if "dynamics" in sys.argv else record_damping() if "damping" in sys.argv else record_steady() if "steady" in sys.argv else (record(), record_steady())
     else:
         print(__doc__)
