@@ -630,6 +630,55 @@ int fv3_apply_tendencies(fv3_ctx *, const fv3_field *u, const fv3_field *v, cons
                          const fv3_field *ew_x, const fv3_field *ew_y, const fv3_field *ew_z, const fv3_field *ev_um, const fv3_field *ev_up,
                          const fv3_field *ev_vm, const fv3_field *ev_vp, double dt, void *stream);
 
+/* ---- dry convective adjustment of the sponge layers (fv3_subgridz.hip) ------------------------------------------------------------
+ * FV3 fv_sg.F90, subroutine fv_subgrid_z in its non-hydrostatic form; pyFV3 DryConvectiveAdjustment, which the reference driver runs
+ * after every step_dynamics when fv_sg_adj > 0 and whose wind tendencies fv3_apply_tendencies then applies.  Restated (the source is
+ * not in the reference tree: unpinned).  Levels are 0-based from the top; everything in the build's Real, every
+ * sum, product and quotient rounded on its own in the order written; min(a, b) = a < b ? a : b, max(a, b) = a > b ? a : b,
+ * dim(a, b) = max(a - b, 0), comparisons plain IEEE.
+ *
+ * params: dt (s), tau (s, the namelist's fv_sg_adj), t_min, t_max (K), kbot (levels the operator works on; clipped to nz).  Formed in
+ * double and cast once: rdt = 1 / dt, fra = dt / tau; grav, g2 = 0.5 grav, cv_air = cp_air - rdgas (the context's constants),
+ * xvir = rvgas / rdgas - 1 (0 when water is NULL); cv_vap, c_liq, c_ice of the fv3_water.  ustar2 = 1e-4, ri_max = 1, ri_min = 0.25.
+ *
+ * Working copy on levels 0 .. kbot-1: u0 = ua, v0 = va, w0 = w, t0 = pt, q0_i = q_i.  Per level (an absent species is 0):
+ *   q_liq = ql + qr;  q_sol = (qi + qs) + qg
+ *   cvm   = (((1 - ((qv + q_liq) + q_sol)) * cv_air + qv * cv_vap) + q_liq * c_liq) + q_sol * c_ice          (dry: cv_air)
+ *   qcon  = (((ql + qi) + qs) + qr) + qg                                                                     (dry: 0)
+ *   tvol(k) = gz[k] + 0.5 * ((u0 * u0 + v0 * v0) + w0 * w0)
+ * Three passes n = 1, 2, 3 with ratio = (Real)n / (Real)3.  At the start of a pass, from the current working copy, gzh = 0 and for
+ * k = kbot-1 down to 0:  gz[k] = gzh - g2 * delz[k];  te[k] = cvm[k] * t0[k] + tvol(k);  gzh = gzh - grav * delz[k].
+ * Then for k = kbot-1 down to 1 (upper level m = k-1, lower level k), each pair seeing what the pair below it left:
+ *   tv1 = t0[m] * ((1 + xvir * qv[m]) - qcon[m]);  tv2 likewise at k;  pt1 = tv1 / pkz[m];  pt2 = tv2 / pkz[k]
+ *   ri  = ((gz[m] - gz[k]) * (pt1 - pt2)) / ((0.5 * (pt1 + pt2)) * (((u0[m] - u0[k])^2 + (v0[m] - v0[k])^2) + ustar2))
+ *   if (tv1 > t_max && tv1 > tv2) ri = 0;  else if (tv2 < t_min) ri = min(ri, 0.1)
+ *   pm = delp[k] / (peln[k+1] - peln[k]);  ri_ref = min(ri_max, ri_min + ((ri_max - ri_min) * dim(400e2, pm)) / 200e2)
+ *   k == 1: ri_ref = 4 ri_ref;  k == 2: ri_ref = 2 ri_ref;  k == 3: ri_ref = 1.5 ri_ref
+ *   r = 1 - max(0, ri / ri_ref);  mc = ri < ri_ref ? (((ratio * delp[m]) * delp[k]) / (delp[m] + delp[k])) * (r * r) : 0
+ *   if (mc > 0): for X in every tracer, u0, v0, te, w0:  h0 = mc * (X[k] - X[m]);  X[m] = X[m] + h0 / delp[m];  X[k] = X[k] - h0 / delp[k]
+ *                for kk in (m, k): qcon[kk], cvm[kk] from the mixed species;  t0[kk] = (te[kk] - tvol(kk)) / cvm[kk]
+ * (te keeps its mixed value within a pass.)  After the third pass, in a column where some mc > 0 occurred: if fra < 1 every working
+ * value becomes X = X_in + (X - X_in) * fra; on levels 0 .. kbot-1  u_dt = rdt * (u0 - ua), v_dt = rdt * (v0 - va), pt = t0, w = w0,
+ * q_i = q0_i.  A column without any mc > 0 is not stored (pt, w and the tracers stay bitwise) and gets zero tendencies; so do levels
+ * kbot .. nz-1 of every column.  u_dt, v_dt are assigned on the compute cells of levels 0 .. nz-1; nothing else outside levels
+ * 0 .. kbot-1 of the compute cells of pt, w and the tracers is written.  q_con, cappa and pkz of the state are not updated.
+ *
+ * water (NULL: dry): species that are given must be among `tracers`; they are mixed by the main walk, the other tracers by a second
+ * kernel from the stored mc.  work: scratch fields of the context's 3-D layout, 2 + n_tracers of them, and 3 more when a tracer is
+ * not a water species (t0, w0, one copy per tracer, mc of the three passes); u_dt and v_dt hold u0, v0 during the call.
+ * FV3_ERR_ARG (a message that names the field, nothing launched, no field changed): a null context or params; a null or wrongly
+ * shaped field (every 3-D field of the layout has the nz + 1 levels peln needs); a written field (pt, w, a tracer, u_dt, v_dt, a
+ * work field) that is also given as another argument; a species that is not among the tracers; dt <= 0 or not finite; tau <= 0;
+ * kbot < 0; too few work fields.  kbot < 3: FV3_OK, the tendencies are zeroed and nothing else happens. */
+typedef struct fv3_subgridz_params {
+  double dt, tau, t_min, t_max;
+  int kbot;
+} fv3_subgridz_params;
+int fv3_subgrid_z(fv3_ctx *, const fv3_subgridz_params *, const fv3_water *water /* NULL: dry */, int n_tracers,
+                  const fv3_field *const *tracers, const fv3_field *ua, const fv3_field *va, const fv3_field *w, const fv3_field *pt,
+                  const fv3_field *delp, const fv3_field *delz, const fv3_field *peln, const fv3_field *pkz, const fv3_field *u_dt,
+                  const fv3_field *v_dt, int n_work, const fv3_field *const *work, void *stream);
+
 /* ---- driver diagnostics (fv3_diag.hip): what the driver stores every output_frequency steps ------------------------------
  * [REF driver/pace/driver/diagnostics.py].  Neither entry allocates: the caller owns `out`, a contiguous device array in the
  * build's Real.  Neither reads a halo cell or the pad level.

@@ -18,7 +18,7 @@ CSRC = os.path.join(HERE, "csrc")
 ROOT = os.path.dirname(HERE)
 HOSTEMU_DIR = os.path.join(ROOT, "tests", "_hostemu")
 
-SOURCES = ["fv3_ctx.hip", "fv3_tp2d.hip", "fv3_tp2x.hip", "fv3_tp4.hip", "fv3_tp4x.hip", "fv3_a2b.hip", "fv3_csw.hip", "fv3_dsw.hip", "fv3_wind.hip", "fv3_nh.hip", "fv3_riem.hip", "fv3_dz.hip", "fv3_del2x.hip", "fv3_pgf.hip", "fv3_step.hip", "fv3_halo.hip", "fv3_tracer.hip", "fv3_remap.hip", "fv3_c2l.hip", "fv3_diag.hip", "fv3_fillz.hip", "fv3_thermo.hip", "fv3_moist.hip", "fv3_negadj.hip", "fv3_satadj.hip", "fv3_hs.hip", "fv3_updphys.hip"]
+SOURCES = ["fv3_ctx.hip", "fv3_tp2d.hip", "fv3_tp2x.hip", "fv3_tp4.hip", "fv3_tp4x.hip", "fv3_a2b.hip", "fv3_csw.hip", "fv3_dsw.hip", "fv3_wind.hip", "fv3_nh.hip", "fv3_riem.hip", "fv3_dz.hip", "fv3_del2x.hip", "fv3_pgf.hip", "fv3_step.hip", "fv3_halo.hip", "fv3_tracer.hip", "fv3_remap.hip", "fv3_c2l.hip", "fv3_diag.hip", "fv3_fillz.hip", "fv3_thermo.hip", "fv3_moist.hip", "fv3_negadj.hip", "fv3_satadj.hip", "fv3_hs.hip", "fv3_updphys.hip", "fv3_subgridz.hip"]
 HEADERS = ["fv3_common.h", "fv3_box.h", "fv3_switch.h", "fv3_ops.h", "fv3_csw_plan.h", "fv3_col_plan.h", "fv3_kwalk.h", "fv3_ppm.h", "fv3_a2b.h", "fv3_math.h", "fv3_agpr.h", "fv3_march.h", "fv3_moist.h", "fv3_satadj.h", os.path.join("..", "..", "include", "fv3_mi355x.h")]
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

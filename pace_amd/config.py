@@ -105,6 +105,13 @@ class AcousticDynamicsConfig:
     c2l_ord: int = 4
     # negative tracer means are filled in the vertical (fillz) at the end of the remap; FV3's namelist default is off
     fill: bool = False
+    # time scale (s) of the dry convective adjustment of the sponge layers (fv_subgrid_z); 0 = off, FV3's namelist default
+    fv_sg_adj: int = 0
+
+    @property
+    def do_dry_convective_adjustment(self) -> bool:
+        """The reference's name: ``fv_sg_adj > 0`` runs DryConvectiveAdjustment after every ``step_dynamics``."""
+        return self.fv_sg_adj > 0
 
     def validate(self):
         """The kernels are specialised like the reference configs; anything else fails loudly."""

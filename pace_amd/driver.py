@@ -15,7 +15,10 @@ say ``"neg_adj": true`` (otherwise ``false``); with ``--moist`` and ``do_sat_adj
 overrides the yaml) FV3's saturation adjustment runs inside every remap with the yaml's ``tau_*`` / ``ql_gen`` ... keys
 (``pace_amd.stencils.SatAdjustConfig``) and the start-up line and the json say ``"sat_adj": true`` (otherwise ``false``); with ``--held-suarez``
 (needs ``--temperature --remap --latlon-winds``) every step ends with the Held-Suarez forcing and ``ApplyPhysicsToDycore`` and the start-up line and
-the json say ``"forcing": "held_suarez"`` (otherwise ``"none"``) -- and writes
+the json say ``"forcing": "held_suarez"`` (otherwise ``"none"``); with ``fv_sg_adj`` above 0 in the yaml's ``dycore_config`` (``--dry-adjust yaml``, the default; ``on`` / ``off`` override
+the yaml; needs ``--temperature --remap --latlon-winds``, and with ``yaml`` the driver says in one line that the key is ignored where they are absent) every step
+ends with the dry convective adjustment of the sponge layers (``DryConvectiveAdjustment``, FV3's ``fv_subgrid_z``) and ``ApplyPhysicsToDycore``, and the start-up line and
+the json say ``"dry_convective_adjustment": true`` (otherwise ``false``) -- and writes
 the per-step times in the layout the reference's performance collector uses
 (``{"times": {<timer>: {"hits": n, "times": [[...per step...] per rank]}}}``, timers ``mainloop``, ``DynCore``,
 ``TracerAdvection``, ``Remapping`` [REF tests/main/driver/test_driver.py:77-121]).  With ``--tracers N --remap`` the step is the
@@ -163,6 +166,20 @@ def filter_diagnostics(block, known):
     return block, dropped
 
 
+DRY_ADJUST_NEEDS = "--temperature --remap --latlon-winds: fv_subgrid_z reads the temperature and the eastward / northward winds of the step's end state"
+
+
+def resolve_dry_adjust(option: str, dycore_config: dict, prerequisites: bool):
+    """Whether every step ends with the dry convective adjustment: the yaml's ``dycore_config.fv_sg_adj > 0`` (absent = 0 = off) unless
+    ``--dry-adjust on|off`` overrides it -> (on, ignored): ``ignored`` when the yaml asks for it and ``--temperature --remap
+    --latlon-winds`` are not all given (the driver says so and goes on); ``on`` without them is refused by the caller."""
+    if option not in ("yaml", "on", "off"):
+        raise ValueError(f"--dry-adjust {option!r}: yaml, on or off")
+    asked = int(dycore_config.get("fv_sg_adj", 0) or 0) > 0
+    want = asked if option == "yaml" else option == "on"
+    return bool(want and prerequisites), bool(option == "yaml" and asked and not prerequisites)
+
+
 def resolve_fill(option: str, dycore_config: dict, tracers: int, remap: bool) -> bool:
     """Whether the step fills negative tracer values in the vertical (``fillz`` at the end of the remap): the yaml's
     ``dycore_config.fill`` (absent = false, FV3's namelist default) unless ``--fill on|off`` overrides it; without ``--remap`` or
@@ -201,6 +218,9 @@ def main(argv=None):
     ap.add_argument("--held-suarez", action="store_true",
                     help="end every step with the Held-Suarez (1994) forcing and ApplyPhysicsToDycore (needs --temperature --remap --latlon-winds): Newtonian relaxation of the "
                          "temperature and Rayleigh friction on the low-level winds, applied to the D-grid state with dt_atmos")
+    ap.add_argument("--dry-adjust", choices=("yaml", "on", "off"), default="yaml",
+                    help="end every step with the dry convective adjustment of the sponge layers (FV3 fv_subgrid_z) and ApplyPhysicsToDycore (needs --temperature --remap --latlon-winds): "
+                         "yaml = dycore_config.fv_sg_adj > 0 (absent: off), the key being the relaxation time in seconds; on / off override it")
     ap.add_argument("--diagnostics-path", default=None, help="directory of the diagnostics (overrides diagnostics_config.path of the yaml)")
     ap.add_argument("--no-diagnostics", action="store_true", help="ignore the yaml's diagnostics_config block")
     a = ap.parse_args(argv)
@@ -210,6 +230,9 @@ def main(argv=None):
         sys.exit("--moist needs --temperature --remap: moist_cv sits in the preamble and the remap of DynamicalCore.step_dynamics")
     if a.held_suarez and not (a.temperature and a.remap and a.latlon_winds):
         sys.exit("--held-suarez needs --temperature --remap --latlon-winds: the forcing reads the temperature and the eastward / northward winds of the step's end state")
+    dry_prerequisites = bool(a.temperature and a.remap and a.latlon_winds)
+    if a.dry_adjust == "on" and not dry_prerequisites:
+        sys.exit("--dry-adjust on needs " + DRY_ADJUST_NEEDS)
     if a.neg_adj and not a.moist:
         sys.exit("--neg-adj needs --moist: neg_adj3 works on the six water species of the moist step")
     if a.sat_adj == "on" and not a.moist:
@@ -229,6 +252,12 @@ def main(argv=None):
         from .stencils import SatAdjustConfig
 
         sat_cfg = SatAdjustConfig(**{k: float(v) for k, v in run["sat_adj"].items() if k != "do_sat_adj"})
+
+    dry_adjust, dry_ignored = resolve_dry_adjust(a.dry_adjust, dy, dry_prerequisites)
+    if dry_adjust and a.held_suarez:
+        sys.exit("--held-suarez and the dry convective adjustment exclude each other: both assign the wind tendencies that ApplyPhysicsToDycore applies (--dry-adjust off turns the yaml's fv_sg_adj off)")
+    if dry_adjust and int(dy.get("fv_sg_adj", 0) or 0) <= 0:
+        sys.exit("--dry-adjust on needs dycore_config.fv_sg_adj > 0 in the yaml: the key is the relaxation time of the adjustment in seconds")
 
     import torch
 
@@ -260,6 +289,10 @@ def main(argv=None):
     forcing = "held_suarez" if a.held_suarez else "none"
     say(f'"forcing": "{forcing}"' + ("  (Held-Suarez tendencies from the step's end state, applied to u, v, pt by ApplyPhysicsToDycore with dt_atmos)" if a.held_suarez
                                      else "  (an unforced initial-value problem; --held-suarez with --temperature --remap --latlon-winds: Held-Suarez forcing)"))
+    say(f'"dry_convective_adjustment": {str(dry_adjust).lower()}' + ("" if a.dry_adjust == "yaml" else f" (--dry-adjust {a.dry_adjust})")
+        + (f"  (fv_subgrid_z on the top {min(int(dy.get('n_sponge', 48)), run['nz'])} levels with fv_sg_adj = {int(dy.get('fv_sg_adj', 0))} s after every step_dynamics, its wind tendencies applied by ApplyPhysicsToDycore)" if dry_adjust
+           else (f"  (fv_sg_adj: {dy.get('fv_sg_adj')} of the yaml is ignored without " + DRY_ADJUST_NEEDS.split(":")[0] + ")" if dry_ignored
+                 else "  (no convective adjustment; fv_sg_adj > 0 in the yaml with --temperature --remap --latlon-winds: fv_subgrid_z on the sponge layers)")))
     say(f'"grid": {json.dumps(grid_entry(run["grid"]))}' + ("  (Schmidt transform of the generated corner positions; divergence damping in its stretched form)" if grid_entry(run["grid"]) != "uniform"
                                                             else "  (grid_config.config.stretch_factor / lon_target / lat_target: a grid refined about a target point)"))
     if run["init"] == "analytic" and str(run["case"]).startswith("baroclinic"):
@@ -283,7 +316,7 @@ def main(argv=None):
     kw = {k: dy[k] for k in ("k_split", "n_split") if k in dy}
     h = DycoreHarness(nx_tile=run["nx_tile"], nz=run["nz"], layout=run["layout"], dt_atmos=run["dt_atmos"], world_size=world, proc=rank,
                       device=f"cuda:{local_rank}", dtype=dtype, verbose=(rank == 0), init=init, config_overrides={k: v for k, v in dy.items() if k not in ("k_split", "n_split", "fill")},
-                      n_tracers=a.tracers, hord_tr=int(dy.get("hord_tr", 8)), remap=a.remap, fill=fill, latlon_winds=a.latlon_winds, temperature=a.temperature, moist=a.moist, neg_adj=a.neg_adj, sat_adj=sat_adj, sat_adjust_config=sat_cfg, held_suarez=a.held_suarez, **harness_grid_kwargs(run["grid"]), **kw)
+                      n_tracers=a.tracers, hord_tr=int(dy.get("hord_tr", 8)), remap=a.remap, fill=fill, latlon_winds=a.latlon_winds, temperature=a.temperature, moist=a.moist, neg_adj=a.neg_adj, sat_adj=sat_adj, sat_adjust_config=sat_cfg, held_suarez=a.held_suarez, dry_convective_adjustment=dry_adjust, **harness_grid_kwargs(run["grid"]), **kw)
     if run["device_sync"]:
         h.sf.set_device_sync(True)
     if a.restart:
@@ -371,7 +404,7 @@ def main(argv=None):
         sdpd = run["dt_atmos"] / mean
         out = a.out or f"{run['experiment']}_fv3_mi355x.json"
         json.dump({"setup": {"experiment": run["experiment"], "nx_tile": run["nx_tile"], "nz": run["nz"], "layout": list(run["layout"]), "dt_atmos": run["dt_atmos"],
-                             "k_split": h.cfg.k_split, "n_split": h.cfg.n_split, "n_gpus": world, "backend": "hip:gfx950", "dycore_only": True, "acoustic_only": not (a.tracers or a.remap), "tracers": a.tracers, "remap": bool(a.remap), "fill": fill, "pt": pt_form, "thermodynamics": thermo, "neg_adj": bool(a.neg_adj), "sat_adj": sat_adj, "forcing": forcing, "grid": grid_entry(run["grid"]), "finite": ok,
+                             "k_split": h.cfg.k_split, "n_split": h.cfg.n_split, "n_gpus": world, "backend": "hip:gfx950", "dycore_only": True, "acoustic_only": not (a.tracers or a.remap), "tracers": a.tracers, "remap": bool(a.remap), "fill": fill, "pt": pt_form, "thermodynamics": thermo, "neg_adj": bool(a.neg_adj), "sat_adj": sat_adj, "forcing": forcing, "dry_convective_adjustment": dry_adjust, "grid": grid_entry(run["grid"]), "finite": ok,
                              "note": ("a step here is k_split AcousticDynamics calls; the reference's dycore_only mainloop (DynamicalCore.step_dynamics) also runs tracer "
                                       "advection and the Lagrangian-to-Eulerian remap (--tracers N --remap add them): not comparable with the reference's 'mainloop' timer")
                              if not (a.tracers and a.remap) else

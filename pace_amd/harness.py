@@ -17,6 +17,10 @@ grid about the target with a Schmidt transform (``pace_amd.grid.SchmidtTransform
 ``held_suarez`` (needs ``temperature``, ``remap`` and ``latlon_winds``; ``held_suarez_config``: a ``pace_amd.stencils.HeldSuarezConfig``) adds the
 second half of the reference driver's step [REF driver/pace/driver/driver.py:494-530]: after ``step_dynamics`` the Held-Suarez forcing forms
 ``u_dt``, ``v_dt``, ``pt_dt`` from the end state and ``ApplyPhysicsToDycore`` applies them with ``dt_atmos`` (timer clocks "HeldSuarez", "ApplyPhysics").
+``dry_convective_adjustment`` (needs ``temperature``, ``remap`` and ``latlon_winds``; not together with ``held_suarez``: both assign ``u_dt``, ``v_dt``) is the
+reference's ``fv_sg_adj > 0``: after ``step_dynamics`` ``DryConvectiveAdjustment`` (``fv_subgrid_z`` on the top ``n_sponge`` levels, time scale
+``config.fv_sg_adj``; with ``moist`` the six water species are passed, otherwise it runs dry) mixes ``pt``, ``w`` and the tracers and forms ``u_dt``, ``v_dt``,
+which ``ApplyPhysicsToDycore`` applies with ``dt_atmos`` and a zero ``pt_dt`` (timer clocks "DryConvectiveAdjustment", "ApplyPhysics").
 ``constants`` (a ``pace_amd.constants.ConstantSet``; None: the project's): the constants the grids and the kernels are made with, e.g. ``OMEGA = 0`` for a planet that does not turn.
 """
 from __future__ import annotations
@@ -94,11 +98,16 @@ class DycoreHarness:
         lat_target: float = -90.0,
         held_suarez: bool = False,
         held_suarez_config=None,
+        dry_convective_adjustment: bool = False,
         constants=None,
         _testing_token=None,
     ):
         if held_suarez and not (temperature and remap and latlon_winds):
             raise ValueError("held_suarez=True needs temperature=True, remap=True and latlon_winds=True: the forcing reads the temperature and the eastward / northward winds of the step's end state")
+        if dry_convective_adjustment and not (temperature and remap and latlon_winds):
+            raise ValueError("dry_convective_adjustment=True needs temperature=True, remap=True and latlon_winds=True: fv_subgrid_z reads the temperature and the eastward / northward winds of the step's end state")
+        if dry_convective_adjustment and held_suarez:
+            raise ValueError("dry_convective_adjustment=True and held_suarez=True exclude each other: both assign the wind tendencies u_dt, v_dt that ApplyPhysicsToDycore applies")
         if fill and not remap:
             raise ValueError("fill=True needs remap=True: the vertical filling of negative tracer values is the last tracer step of the remap")
         if temperature and not remap:
@@ -180,8 +189,9 @@ class DycoreHarness:
                 self._load_restart_tracer(vapor, init_data, "sphum")
             self._init_temperature(vapor, hord_tr, latlon_winds)
             self._init_held_suarez(held_suarez, held_suarez_config)
+            self._init_dry_adjust(dry_convective_adjustment)
             return
-        self.held_suarez = self.apply_physics = None
+        self.held_suarez = self.apply_physics = self.dry_adjust = None
         self.dyn =AcousticDynamics(self.layout, self.grids, self.sf, config=self.cfg, phis=self.state.phis, state=self.state)
         # shared D-grid interface winds must be single-valued across sub-domains (they are in any
         # physical state; the per-rank white noise of the synthetic recipe breaks it)
@@ -284,6 +294,20 @@ class DycoreHarness:
         self.apply_physics = ApplyPhysicsToDycore(self.sf, qf, self.grids, comm=self.layout)
         self.u_dt, self.v_dt, self.pt_dt = qf.zeros(("x", "y", "z"), "m/s**2"), qf.zeros(("x", "y", "z"), "m/s**2"), qf.zeros(("x", "y", "z"), "K/s")
 
+    def _init_dry_adjust(self, on):
+        """dry_convective_adjustment=True: the step ends with ``DryConvectiveAdjustment`` on the end state and ``ApplyPhysicsToDycore`` with
+        ``dt_atmos``; the operators, the work fields and the three tendency buffers (``pt_dt`` stays zero) are made here."""
+        self.dry_adjust = None
+        if not on:
+            return
+        from .stencils import ApplyPhysicsToDycore, DryConvectiveAdjustment
+
+        qf = self.sf.quantity_factory
+        self.dry_adjust = DryConvectiveAdjustment(self.sf, qf, self.grids, n_sponge=self.cfg.n_sponge, fv_sg_adj=self.cfg.fv_sg_adj,
+                                                  water_species=self.dycore.water if self.moist else None, tracers=self.tracers)
+        self.apply_physics = ApplyPhysicsToDycore(self.sf, qf, self.grids, comm=self.layout)
+        self.u_dt, self.v_dt, self.pt_dt = qf.zeros(("x", "y", "z"), "m/s**2"), qf.zeros(("x", "y", "z"), "m/s**2"), qf.zeros(("x", "y", "z"), "K/s")
+
     def to_temperature(self):
         """The state's ``pt`` from the loop's form ``T_v / pkz`` (what every ``init`` and a default-mode restart file hold) to the
         temperature in K, ``pkz`` rebuilt from the state, ``ps`` from ``pe``; ``omga`` is not touched.  It reads the state's own
@@ -305,6 +329,12 @@ class DycoreHarness:
                 s = self.state
                 with timer.clock("HeldSuarez"):
                     self.held_suarez(s.ua, s.va, s.pt, s.delp, self.u_dt, self.v_dt, self.pt_dt, self.cfg.dt_atmos)
+                with timer.clock("ApplyPhysics"):
+                    self.apply_physics(s, self.u_dt, self.v_dt, self.pt_dt, self.cfg.dt_atmos)
+            if self.dry_adjust is not None:  # the reference's fv_sg_adj > 0: DycoreToPhysics runs fv_subgrid_z, ApplyPhysicsToDycore its wind tendencies
+                s = self.state
+                with timer.clock("DryConvectiveAdjustment"):
+                    self.dry_adjust(s, self.u_dt, self.v_dt, self.cfg.dt_atmos)
                 with timer.clock("ApplyPhysics"):
                     self.apply_physics(s, self.u_dt, self.v_dt, self.pt_dt, self.cfg.dt_atmos)
             return

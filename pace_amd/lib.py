@@ -133,6 +133,10 @@ class fv3_held_suarez(C.Structure):
     _fields_ = [(n, C.c_double) for n in HS_PARAMS]
 
 
+class fv3_subgridz_params(C.Structure):
+    _fields_ = [(n, C.c_double) for n in "dt tau t_min t_max".split()] + [("kbot", C.c_int)]
+
+
 _D = C.c_double
 _I = C.c_int
 _S = C.c_void_p  # stream
@@ -204,6 +208,7 @@ _PROTOS = {
     "fv3_cubed_to_latlon": (C.c_int, [C.c_void_p, _I] + [F] * 8 + [_S]),
     "fv3_held_suarez_tend": (C.c_int, [C.c_void_p, P(fv3_held_suarez)] + [F] * 8 + [_D, _D, _S]),
     "fv3_apply_tendencies": (C.c_int, [C.c_void_p] + [F] * 21 + [_D, _S]),
+    "fv3_subgrid_z": (C.c_int, [C.c_void_p, P(fv3_subgridz_params), P(fv3_water), _I, P(F)] + [F] * 10 + [_I, P(F), _S]),
     "fv3_diag_pack": (C.c_int, [C.c_void_p, F, _I, _I, _I, _I, C.c_void_p, C.c_long, _S]),
     "fv3_diag_column_integral": (C.c_int, [C.c_void_p, F, F, C.c_void_p, C.c_long, _S]),
 }

@@ -656,6 +656,57 @@ class HeldSuarezForcing(_Op):
                      float(self.ptop if ptop is None else ptop), float(dt))
 
 
+class DryConvectiveAdjustment(_Op):
+    """The dry convective adjustment of the sponge layers (FV3 ``fv_subgrid_z``, ``fv_sg.F90``; pyFV3's ``DryConvectiveAdjustment``,
+    which the reference driver runs after every ``step_dynamics`` when ``fv_sg_adj > 0``): on the top ``n_sponge`` levels a pair of
+    neighbouring levels whose Richardson number is below a reference value mixes momentum, total energy, ``w`` and every tracer, in
+    three passes, and the change is relaxed with ``timestep / fv_sg_adj`` (``fv3_subgrid_z`` in include/fv3_mi355x.h holds the
+    algorithm).  Call as the reference's ``(state, u_dt, v_dt, timestep)``: it reads ``state.ua``, ``va`` (eastward / northward),
+    ``w``, ``pt`` (the temperature in K, so the call belongs after ``DynamicalCore.step_dynamics``), ``delp``, ``delz``, ``peln``,
+    ``pkz`` and the tracers; ``u_dt``, ``v_dt`` are assigned, not accumulated (zero below the sponge and in columns that did not
+    mix); ``pt``, ``w`` and the tracers change in place on the top levels.  ``q_con``, ``cappa`` and ``pkz`` of the state are left as
+    they are, as in FV3: the preamble of the next step rebuilds them.  The non-hydrostatic form only.
+
+    ``tracers``: the dict (or list) of tracer quantities that are mixed; ``water_species``: a :class:`WaterSpecies` whose species
+    are among them (None: dry -- constant heat capacity, no virtual effect).  ``kbot = min(n_sponge, nz)`` (below 3 the operator
+    only zeroes the tendencies), ``t_min`` = 160 K where the model top ``ptop`` is below 2 Pa, else 165 K, ``t_max`` = 315 K where
+    ``kbot < min(nz, 24)``, else 325 K.  The work fields (one per tracer, two for ``pt`` and ``w``, three more when a tracer is not
+    a water species) are allocated here, once."""
+
+    def __init__(self, stencil_factory, quantity_factory=None, grid_data=None, *, n_sponge, fv_sg_adj, water_species=None, tracers=None, hydrostatic=False, ptop=None):
+        import ctypes as C
+
+        from . import lib as _lib
+
+        super().__init__(stencil_factory, quantity_factory, grid_data)
+        if not float(fv_sg_adj) > 0.0:
+            raise ValueError(f"DryConvectiveAdjustment: fv_sg_adj = {fv_sg_adj} must be a positive time scale in seconds (0 or less turns the adjustment off in the namelist)")
+        if hydrostatic or getattr(self.sf.config, "hydrostatic", False):
+            raise NotImplementedError("DryConvectiveAdjustment: only the non-hydrostatic form of fv_subgrid_z is built")
+        nz = int(self.sf.grids[0].nz)
+        self.tau = float(fv_sg_adj)
+        self.kbot = min(int(n_sponge), nz)
+        self.ptop = float(self.sf.grids[0].ptop if ptop is None else ptop)
+        self.t_min = 160.0 if self.ptop < 2.0 else 165.0
+        self.t_max = 315.0 if self.kbot < min(nz, 24) else 325.0
+        self.water = water_species
+        self.tracers = list(tracers.values()) if isinstance(tracers, dict) else list(tracers or [])
+        species = [] if water_species is None else [q for q in water_species.species.values() if q is not None]
+        n_passive = sum(1 for q in self.tracers if not any(q is w for w in species))
+        self.n_work = 2 + len(self.tracers) + (3 if n_passive else 0)
+        self.work = [self.qf.zeros(_CELL, "") for _ in range(self.n_work)]
+        self._work = (_lib.F * self.n_work)(*[C.pointer(q.field) for q in self.work])
+        self._tracers = (_lib.F * max(len(self.tracers), 1))(*[C.pointer(q.field) for q in self.tracers])
+        self.params = _lib.fv3_subgridz_params(0.0, self.tau, self.t_min, self.t_max, max(self.kbot, 0))
+        self._pref = C.byref(self.params)
+
+    def __call__(self, state, u_dt, v_dt, timestep):
+        self.params.dt = float(timestep)
+        self.sf.call("subgrid_z", self._pref, None if self.water is None else self.water.cref, len(self.tracers), self._tracers,
+                     state.ua.fref, state.va.fref, state.w.fref, state.pt.fref, state.delp.fref, state.delz.fref, state.peln.fref, state.pkz.fref,
+                     u_dt.fref, v_dt.fref, self.n_work, self._work)
+
+
 class ApplyPhysicsToDycore(_Op):
     """Cell-centre tendencies applied to the D-grid state (FV3 ``fv_update_phys``; pyFV3's ``ApplyPhysicsToDycore``): call as the
     reference's ``(state, u_dt, v_dt, pt_dt, dt)`` with ``u_dt``, ``v_dt`` the eastward / northward wind tendencies (m/s^2) and
@@ -666,8 +717,9 @@ class ApplyPhysicsToDycore(_Op):
     call starts with a one-cell halo update of ``u_dt``, ``v_dt`` -- geographic components, exchanged as two scalars (``comm``: a
     :class:`pace_amd.halo.Layout`, None = every rank in this process).
 
-    Not built, and refused where they can be asked for: tracer tendencies, the moist ``delp`` adjustment, nudging, the dry
-    convective adjustment."""
+    Not built, and refused where they can be asked for: tracer tendencies, the moist ``delp`` adjustment, nudging.  ``do_sg_conv``
+    (FV3's flag for a convection scheme inside ``fv_update_phys``) is refused too: the dry convective adjustment of ``fv_sg_adj`` is the
+    caller's step before this one, :class:`DryConvectiveAdjustment`."""
 
     def __init__(self, stencil_factory, quantity_factory=None, grid_data=None, comm=None, *, tracer_tendencies=None, nudge=False, do_sg_conv=False):
         from .grid import UPDPHYS_FIELDS
@@ -678,7 +730,7 @@ class ApplyPhysicsToDycore(_Op):
         if nudge:
             raise NotImplementedError("ApplyPhysicsToDycore: nudging is not built")
         if do_sg_conv:
-            raise NotImplementedError("ApplyPhysicsToDycore: the dry convective adjustment (fv_subgridz) is not built")
+            raise NotImplementedError("ApplyPhysicsToDycore: do_sg_conv is not built here, the dry convective adjustment (fv_subgridz) is the caller's DryConvectiveAdjustment before this call")
         missing = [n for n in UPDPHYS_FIELDS if n not in self.sf.grids[0].fields]
         if missing:
             raise ValueError(f"ApplyPhysicsToDycore: the grid data lacks {', '.join(missing)} (pace_amd.grid.make_grid forms them)")
